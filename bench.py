@@ -11,7 +11,8 @@ latent_pose_reenactment_amd.parallel (weak scaling).
 `--workload finetune_step` = BASELINE configs[1] (finetuning-base.yaml; the reference refuses multi-GPU fine-tuning): at N = 1 the
 default run also measures it in a child process and reports it under "finetune_step".
 
-Prints ONE JSON line on rank 0 (see README/DESIGN for the field definitions)."""
+Prints ONE JSON line on rank 0, at most 6 KB (see README/DESIGN for the field definitions; ``result_line``): the headline and numbers-only
+side lines.  `--detail FILE` writes the whole record, `--dump-outputs DIR` the arrays of the last timed step."""
 import argparse
 import json
 import os
@@ -682,6 +683,127 @@ def measured_parity(mode, workload):
     return out
 
 
+RESULT_LINE_MAX_BYTES = 6144      # a driver reads the END of stdout: a longer line loses its head (metric, value, ms_per_step) there
+
+
+def _summary(rec, keys):
+    """the listed keys of a record that are present; a failed side measurement ({'error': ...}) passes its error through, shortened"""
+    if not isinstance(rec, dict):
+        return rec
+    if 'error' in rec:
+        return {'error': str(rec['error'])[:300]}
+    return {k: rec[k] for k in keys if k in rec}
+
+
+def _finite(obj):
+    """NaN / inf -> None: the line must parse with a strict JSON reader"""
+    if isinstance(obj, float):
+        return obj if obj == obj and abs(obj) != float('inf') else None
+    if isinstance(obj, dict):
+        return {k: _finite(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_finite(v) for v in obj]
+    return obj
+
+
+def result_line(out):
+    """-> the ONE stdout line (a string of at most RESULT_LINE_MAX_BYTES): the headline fields and numbers-only summaries of the side
+    measurements.  The whole record ``out`` -- notes, per-operand-mode splits, the side measurements in full -- goes to ``--detail FILE``."""
+    line = {k: out[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                                'vs_baseline', 'data') if k in out}
+    line['dtype'] = str(out.get('dtype', '')).split(' -- ')[0][:200]
+    cfg = dict(out.get('config') or {})
+    if isinstance(cfg.get('streams'), dict):
+        cfg['streams'] = cfg['streams'].get('concurrent_branches')
+    line['config'] = cfg
+    line['roofline'] = _summary(out.get('roofline'), ('kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'frac_in_graph', 'frac_mfma_work',
+                                                      'traffic', 'traffic_stale', 'mfma_busy_fraction_pmc', 'launches', 'avg_launch_us'))
+    line['step_mfma_utilisation'] = _summary(out.get('step_mfma_utilisation'), ('algorithmic_tflop_per_step', 'achieved_tflops', 'frac_of_bf16_peak'))
+    p = out.get('parity')
+    if isinstance(p, dict):
+        tie = (p.get('gradients') or {}).get('tie_masked_worst_rel_l2') or {}
+        line['parity'] = {'status': p.get('status'), 'gates_met': p.get('gates_met'), 'worst_forward': p.get('worst'),
+                          'worst_gradient_tie_masked': list(max(tie.items(), key=lambda kv: kv[1])) if tie else None}
+    side = {'drive': ('value', 'unit', 'ms_per_frame', 'launch_mode'),
+            'strict_mode_bf16x3': ('value', 'unit', 'ms_per_step', 'roofline_frac'),
+            'fp16_generator_and_critic_option': ('value', 'unit', 'ms_per_step', 'env', 'gates_met'),
+            'finetune_step': ('value', 'unit', 'ms_per_step', 'steps', 'warmup'),
+            'cpu_baseline': ('value', 'unit', 'cores', 'kind', 'cpu_model'),
+            'single_gpu_same_workload': ('value', 'unit', 'n_gpus', 'steps', 'ms_per_step'),
+            'replicas': ('bit_identical_parameters', 'parameters', 'by_group', 'after_steps'),
+            'gradient_exchange': ('exposed_comm_ms_per_step', 'backend', 'reduce_op')}
+    for k, keys in side.items():
+        if k in out:
+            line[k] = _summary(out[k], keys)
+    if isinstance(out.get('drive'), dict) and isinstance(out['drive'].get('batch_8'), dict):
+        line['drive']['batch_8'] = _summary(out['drive']['batch_8'], ('value', 'unit', 'ms_per_frame'))
+    if isinstance(out.get('finetune_step'), dict) and isinstance(out['finetune_step'].get('roofline'), dict):
+        line['finetune_step']['roofline_frac'] = out['finetune_step']['roofline'].get('frac')
+    if isinstance(out.get('strict_mode_bf16x3'), dict) and isinstance(out['strict_mode_bf16x3'].get('parity'), dict):
+        line['strict_mode_bf16x3']['parity_gates_met'] = out['strict_mode_bf16x3']['parity'].get('gates_met')
+    if isinstance(out.get('cpu_baseline'), dict) and isinstance(out['cpu_baseline'].get('one_thread'), dict):
+        line['cpu_baseline']['one_thread_value'] = out['cpu_baseline']['one_thread'].get('value')
+    line['roofline_other'] = {k[len('roofline_'):]: _summary(v, ('bound', 'achieved', 'unit', 'frac')) for k, v in out.items()
+                              if k.startswith('roofline_')}
+    s = json.dumps(_finite(line))
+    if len(s) > RESULT_LINE_MAX_BYTES:         # (never with the records this file builds; the headline must survive anything)
+        s = json.dumps(_finite({k: line[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step') if k in line}))
+    return s
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """``--dump-outputs DIR``: every array of ``outputs`` (what the timed step function returned in its last step: nested dicts / lists of
+    tensors) as DIR/<dotted name>.npy: float64 and integer tensors (and Python floats) as float64, every other one as float32.  All files
+    together stay under DUMP_MAX_BYTES: the budget is shared out smallest array first, and an array larger than its share is written as a
+    fixed sample of its flattened elements (sorted indices drawn from a generator seeded by its name, so every run and every build picks the
+    same elements).  -> {name: (shape, elements written)}"""
+    import re
+    import zlib
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            flat[name] = v.detach()
+        elif isinstance(v, float):
+            flat[name] = torch.tensor(v, dtype=torch.float64)
+        elif isinstance(v, dict):
+            for k in sorted(v, key=str):
+                walk(f'{name}.{k}', v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f'{name}.{i}', x)
+    for k in sorted(outputs):
+        walk(k, outputs[k])
+    flat = {k: t for k, t in flat.items() if not t.is_complex()}
+    wide = {k: t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) for k, t in flat.items()}
+    # elements each array may write: the data budget (256 B of .npy header per file held back) shared out smallest array first
+    cap, left = {}, DUMP_MAX_BYTES - 256 * len(flat)
+    order = sorted(flat, key=lambda k: (flat[k].numel() * (8 if wide[k] else 4), k))
+    for i, k in enumerate(order):
+        width = 8 if wide[k] else 4
+        cap[k] = max(1, min(flat[k].numel(), left // (len(order) - i) // width))
+        left -= cap[k] * width
+    os.makedirs(path, exist_ok=True)
+    written, seen = {}, set()
+    for name, t in flat.items():
+        fname = re.sub(r'[^A-Za-z0-9_.-]', '_', name)
+        assert fname not in seen, f'two outputs map to {fname}.npy'
+        seen.add(fname)
+        v = t.reshape(-1)
+        if v.numel() > cap[name]:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(v.numel(), cap[name], replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        v = v.to('cpu', torch.float64 if wide[name] else torch.float32)
+        arr = v.numpy().reshape(t.shape) if v.numel() == t.numel() else v.numpy()
+        np.save(os.path.join(path, fname + '.npy'), arr)
+        written[name] = (tuple(t.shape), int(v.numel()))
+    return written
+
+
 def self_launch(n):
     import socket
     import subprocess
@@ -729,8 +851,18 @@ def main():
     ap.add_argument('--eager', action='store_true', help='do not capture the step into hipGraphs')
     ap.add_argument('--shapes', default=None, help='write the per-shape conv / wgrad timing table of the instrumented steps (CSV)')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL; gloo only for functional tests)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the timed step returned in its LAST step (training step: all_data, losses_G, '
+                         'losses_D; generator workload: its output dict) as DIR/<name>.npy, float32 / float64, <= 64 MB in all (a larger '
+                         'tensor as a fixed seeded sample of its elements); same arguments -> same inputs and bit-identical outputs run to run '
+                         '(no float atomics on the step), so two builds compare output for output')
+    ap.add_argument('--detail', default=None, metavar='FILE',
+                    help='write the whole result record (notes, per-mode splits, side measurements in full) to FILE as JSON; stdout carries '
+                         'the bounded summary line')
     ap.add_argument('--cpu-worker', default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be >= 1')
     if a.cpu_worker:
         return cpu_worker(a.cpu_worker)
     if a.cpu_baseline_only:
@@ -772,10 +904,12 @@ def main():
 
     from latent_pose_reenactment_amd import hipops
 
+    # every step function returns what a caller of that path receives ({name: tensors}: --dump-outputs writes the timed loop's last one)
     def gen_only_step():
         dd = {'pose_embedding': pose_static, 'dec_keypoints': kp_static}
         tm.generator(dd)
         (dd['fake_rgbs'].mean() + dd['fake_segm'].mean()).backward()
+        return {'generator': dd}
 
     if a.workload == 'generator':
         pose_static = torch.randn(a.batch, args.pose_embedding_size, device=device)
@@ -783,12 +917,17 @@ def main():
         step = gen_only_step
     else:
         def eager_step():
-            holycow.train_step(tm, data, target, opt_G, opt_D, args)
+            return dict(zip(('all_data', 'losses_G', 'losses_D'), holycow.train_step(tm, data, target, opt_G, opt_D, args)))
         step = eager_step
         mode = 'eager'
         if not a.eager:
             try:
-                step = holycow.GraphedTrainStep(tm, opt_G, opt_D, args, data, target, warmup_steps=max(a.warmup, 2))
+                graphed = holycow.GraphedTrainStep(tm, opt_G, opt_D, args, data, target, warmup_steps=max(a.warmup, 2))
+
+                def graph_step():
+                    graphed()
+                    return {'all_data': graphed.all_data, 'losses_G': graphed.losses_G, 'losses_D': graphed.losses_D}
+                step = graph_step
                 mode = 'hipgraph'
             except Exception as ex:        # keep the bench alive: fall back to the eager loop and say so
                 print(f'[bench] hipGraph capture failed ({ex!r}); running eagerly', file=sys.stderr)
@@ -804,9 +943,15 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = None          # (an eager step's outputs are not kept alive through the next step)
+        last = step()
     sync()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        written = dump_outputs(a.dump_outputs, last)
+        sampled = sum(1 for shape, n in written.values() if n != int(torch.Size(shape).numel()))
+        print(f'[bench] --dump-outputs: {len(written)} arrays ({sampled} sampled) of step {a.steps} of {a.steps} -> {a.dump_outputs}', file=sys.stderr)
+    last = None
     # Live per-kernel timing for the roofline entry: HIP events recorded on the launch stream around every conv launch.
     # Graph replays cannot carry per-kernel events, so the instrumented steps run eagerly right after the timed region
     # (same process, same buffers, same kernels); they are not part of `value`.
@@ -1046,11 +1191,21 @@ def main():
                 out['drive']['batch_8'] = {k: v for k, v in drive_fps(args, frames=30, batch=8).items() if k != 'note'}
             except Exception as ex:
                 out['drive'] = {'error': repr(ex)}
-        def child(extra_args, timeout=600):
+        def child(extra_args, timeout=600, env=None):
+            """-> the child's whole result record (its --detail file; its stdout line is the bounded summary)"""
             import subprocess
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-also'] + extra_args,
-                               capture_output=True, text=True, timeout=timeout)
-            return json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+            import tempfile
+            fd, detail = tempfile.mkstemp(suffix='.json', prefix='bench_child_')
+            os.close(fd)
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-also',
+                                    '--detail', detail] + extra_args, capture_output=True, text=True, timeout=timeout, env=env)
+                if os.path.getsize(detail) == 0:
+                    raise RuntimeError(f'child exited with {r.returncode} before its result: {r.stderr[-500:]}')
+                with open(detail) as f:
+                    return json.load(f)
+            finally:
+                os.unlink(detail)
         if world == 1 and a.prec == 'f16' and a.workload in ('finetune_step', 'metatrain_step') and not a.no_also:
             # the strict-parity mode (bf16x3: 3 MFMAs per MAC, fp32-class results) of the SAME workload, measured by the same script in a
             # child process.  Parity status of the two modes: the f16 headline meets the 1e-3 OUTPUT gate of BASELINE.json; the full
@@ -1068,11 +1223,7 @@ def main():
             # on every forward quantity and loss but NOT on the parameter gradients (generator 1.0 - 1.7e-3, critic <= 9.3e-3 tie-masked) -- an option
             # (LP_PREC_G=f16 LP_D_DPASS_PREC=f16), not the headline
             try:
-                import subprocess
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-also', '--no-drive',
-                                    '--workload', a.workload], capture_output=True, text=True, timeout=600,
-                                   env=dict(os.environ, LP_PREC_G='f16', LP_D_DPASS_PREC='f16'))
-                j = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+                j = child(['--no-drive', '--workload', a.workload], env=dict(os.environ, LP_PREC_G='f16', LP_D_DPASS_PREC='f16'))
                 out['fp16_generator_and_critic_option'] = {
                     'value': j['value'], 'unit': j['unit'], 'ms_per_step': j['ms_per_step'], 'env': 'LP_PREC_G=f16 LP_D_DPASS_PREC=f16',
                     'gates_met': {'forward_quantities_and_losses_1e-3': True, 'tie_masked_parameter_gradients_1e-3 (G, D, VGG)': False},
@@ -1093,7 +1244,10 @@ def main():
                 out['cpu_baseline'] = cpu_baseline(args, full=a.cpu_baseline_full, workload=a.workload)
             except Exception as ex:      # never lose the GPU line because of the baseline leg
                 out['cpu_baseline'] = {'error': repr(ex)}
-        print(json.dumps(out))
+        if a.detail:
+            with open(a.detail, 'w') as f:
+                json.dump(out, f)
+        print(result_line(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -9,8 +9,9 @@
 //   registers (block partials + a small reduction), and emits the bias gradient.
 //
 // lp_grid_crop_fwd / lp_grid_crop_bwd: criterions/idt_embed.py:58-83 crop_and_resize -- per-sample bbox [t,b,l,r] -> affine grid
-//   (align_corners=False) -> bilinear sampling with reflection padding, and its adjoint (fp32 atomics; the crop is a 1.8x zoom, so a
-//   source pixel collects from ~3 output pixels).  Replaces affine_grid + grid_sample + their backward (4 ATen launches per image).
+//   (align_corners=False) -> bilinear sampling with reflection padding, and its adjoint as a fixed-order gather per source pixel (the
+//   crop is a 1.8x zoom, so a source pixel collects from ~3 x 3 output pixels; no atomics: the gradient is bit-reproducible run to run).
+//   Replaces affine_grid + grid_sample + their backward (4 ATen launches per image).
 #include "lp_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
@@ -187,55 +188,121 @@ __device__ __forceinline__ float reflect_coord(float in, int size) {
     return fminf(fmaxf(out, 0.f), (float)(size - 1));
 }
 
-template <bool BWD>
+// the sampling position of output column j (or row i) along an axis of `size` pixels, box edges lo / hi: source pixel x0 and fraction f
+// (x0 + 1 is read when x0 + 1 < size).  The forward and backward kernels both call this, so they agree on every tap.
+__device__ __forceinline__ void crop_tap(int j, int out_size, float lo, float hi, int size, int& x0, float& f) {
+    const float xn = (2.f * j + 1.f) / out_size - 1.f;                                         // affine_grid base coordinate
+    const float g = (hi - lo) / size * xn + ((lo + hi) / size - 1.f);
+    const float ix = reflect_coord(((g + 1.f) * size - 1.f) * 0.5f, size);
+    x0 = (int)floorf(ix);
+    f = ix - x0;
+}
+
 __global__ __launch_bounds__(256) void grid_crop_kernel(const float* __restrict__ img, const float* __restrict__ boxes, float* __restrict__ out,
-                                                        const float* __restrict__ dout, float* __restrict__ dimg,
                                                         int N, int C, int H, int W, int Ho, int Wo) {
     const long long total = (long long)N * Ho * Wo;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int j = (int)(idx % Wo), i = (int)((idx / Wo) % Ho), n = (int)(idx / ((long long)Wo * Ho));
     const float t = boxes[n * 4 + 0], b = boxes[n * 4 + 1], l = boxes[n * 4 + 2], r = boxes[n * 4 + 3];
-    const float xn = (2.f * j + 1.f) / Wo - 1.f, yn = (2.f * i + 1.f) / Ho - 1.f;              // affine_grid base coordinates
-    const float gx = (r - l) / W * xn + ((l + r) / W - 1.f), gy = (b - t) / H * yn + ((t + b) / H - 1.f);
-    const float ix = reflect_coord(((gx + 1.f) * W - 1.f) * 0.5f, W), iy = reflect_coord(((gy + 1.f) * H - 1.f) * 0.5f, H);
-    const int x0 = (int)floorf(ix), y0 = (int)floorf(iy);
-    const float fx = ix - x0, fy = iy - y0;
+    int x0, y0;
+    float fx, fy;
+    crop_tap(j, Wo, l, r, W, x0, fx);
+    crop_tap(i, Ho, t, b, H, y0, fy);
     const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
     const bool x1ok = x0 + 1 < W, y1ok = y0 + 1 < H;
     for (int c = 0; c < C; ++c) {
         const size_t base = ((size_t)n * C + c) * H * W;
-        const size_t o = (((size_t)n * C + c) * Ho + i) * Wo + j;
-        if (!BWD) {
-            float v = w00 * img[base + (size_t)y0 * W + x0];
-            if (x1ok) v += w01 * img[base + (size_t)y0 * W + x0 + 1];
-            if (y1ok) v += w10 * img[base + (size_t)(y0 + 1) * W + x0];
-            if (x1ok && y1ok) v += w11 * img[base + (size_t)(y0 + 1) * W + x0 + 1];
-            out[o] = v;
-        } else {
-            const float gq = dout[o];
-            unsafeAtomicAdd(dimg + base + (size_t)y0 * W + x0, w00 * gq);
-            if (x1ok) unsafeAtomicAdd(dimg + base + (size_t)y0 * W + x0 + 1, w01 * gq);
-            if (y1ok) unsafeAtomicAdd(dimg + base + (size_t)(y0 + 1) * W + x0, w10 * gq);
-            if (x1ok && y1ok) unsafeAtomicAdd(dimg + base + (size_t)(y0 + 1) * W + x0 + 1, w11 * gq);
+        float v = w00 * img[base + (size_t)y0 * W + x0];
+        if (x1ok) v += w01 * img[base + (size_t)y0 * W + x0 + 1];
+        if (y1ok) v += w10 * img[base + (size_t)(y0 + 1) * W + x0];
+        if (x1ok && y1ok) v += w11 * img[base + (size_t)(y0 + 1) * W + x0 + 1];
+        out[(((size_t)n * C + c) * Ho + i) * Wo + j] = v;
+    }
+}
+
+// the adjoint as a GATHER: one thread per source pixel (n, y, x) sums the terms (wx * wy) * dout of every output pixel that reads it, in a
+// fixed order (output columns ascending, output rows ascending within each) -- bit-reproducible run to run, no atomics, no memset.
+// Block = one source row y of sample n; LDS: the taps of every output column and row of that sample, and the list of output rows that read
+// row y (compacted in order by wave 0 with a ballot).  Channels in chunks of 4 (accumulators in registers).
+__global__ __launch_bounds__(256) void grid_crop_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ boxes, float* __restrict__ dimg,
+                                                            int C, int H, int W, int Ho, int Wo) {
+    extern __shared__ __attribute__((aligned(16))) int crop_lds[];
+    int* tx0 = crop_lds;                                  // [Wo]
+    float* tfx = (float*)(tx0 + Wo);                      // [Wo]
+    int* ty0 = (int*)(tfx + Wo);                          // [Ho]
+    float* tfy = (float*)(ty0 + Ho);                      // [Ho]
+    int* yl_i = (int*)(tfy + Ho);                         // [Ho] output rows that read source row y
+    float* yl_w = (float*)(yl_i + Ho);                    // [Ho] their row weights
+    __shared__ int ycount;
+    const int n = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
+    const float t = boxes[n * 4 + 0], b = boxes[n * 4 + 1], l = boxes[n * 4 + 2], r = boxes[n * 4 + 3];
+    for (int j = threadIdx.x; j < Wo; j += 256) crop_tap(j, Wo, l, r, W, tx0[j], tfx[j]);
+    for (int i = threadIdx.x; i < Ho; i += 256) crop_tap(i, Ho, t, b, H, ty0[i], tfy[i]);
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        int cnt = 0;
+        for (int i0 = 0; i0 < Ho; i0 += 64) {
+            const int i = i0 + lane;
+            bool hit = false;
+            float wy = 0.f;
+            if (i < Ho) {
+                const int y0 = ty0[i];
+                if (y0 == y) { hit = true; wy = 1.f - tfy[i]; }
+                else if (y0 + 1 == y && y0 + 1 < H) { hit = true; wy = tfy[i]; }
+            }
+            const unsigned long long m = __ballot(hit);
+            if (hit) {
+                const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                yl_i[pos] = i;
+                yl_w[pos] = wy;
+            }
+            cnt += __popcll(m);
         }
+        if (lane == 0) ycount = cnt;
+    }
+    __syncthreads();
+    if (x >= W) return;
+    const int ny = ycount;
+    for (int c0 = 0; c0 < C; c0 += 4) {
+        const int nc = min(4, C - c0);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < Wo; ++j) {
+            const int x0 = tx0[j];
+            float wx;
+            if (x0 == x) wx = 1.f - tfx[j];
+            else if (x0 + 1 == x && x0 + 1 < W) wx = tfx[j];
+            else continue;
+            for (int k = 0; k < ny; ++k) {
+                const float w = wx * yl_w[k];
+                const float* g = dout + (((size_t)n * C + c0) * Ho + yl_i[k]) * Wo + j;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (c < nc) acc[c] += w * g[(size_t)c * Ho * Wo];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < nc) dimg[(((size_t)n * C + c0 + c) * H + y) * W + x] = acc[c];
     }
 }
 
 extern "C" int lp_grid_crop_fwd(const float* images, const float* boxes, float* out, int N, int C, int H, int W, int Ho, int Wo, void* stream) {
     if (!images || !boxes || !out) return lp_set_error(LP_ERR_ARG, "lp_grid_crop_fwd: null pointer");
     const long long total = (long long)N * Ho * Wo;
-    hipLaunchKernelGGL(grid_crop_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, boxes, out,
-                       nullptr, nullptr, N, C, H, W, Ho, Wo);
+    hipLaunchKernelGGL(grid_crop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, boxes, out,
+                       N, C, H, W, Ho, Wo);
     return lp_check_launch("grid_crop_fwd");
 }
 
 extern "C" int lp_grid_crop_bwd(const float* dout, const float* boxes, float* dimages, int N, int C, int H, int W, int Ho, int Wo, void* stream) {
     if (!dout || !boxes || !dimages) return lp_set_error(LP_ERR_ARG, "lp_grid_crop_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dimages, 0, (size_t)N * C * H * W * sizeof(float), st) != hipSuccess) return lp_set_error(LP_ERR_HIP, "hipMemsetAsync failed");
-    const long long total = (long long)N * Ho * Wo;
-    hipLaunchKernelGGL(grid_crop_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, nullptr, boxes, nullptr, dout, dimages,
-                       N, C, H, W, Ho, Wo);
+    if (N < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || H > 65535 || N > 65535)
+        return lp_set_error(LP_ERR_ARG, "lp_grid_crop_bwd: bad shape");
+    const size_t lds = (size_t)(2 * Wo + 4 * Ho) * sizeof(float);
+    if (lds > 60 * 1024) return lp_set_error(LP_ERR_ARG, "lp_grid_crop_bwd: output too large for the tap tables in LDS");
+    hipLaunchKernelGGL(grid_crop_bwd_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N), dim3(256), lds, (hipStream_t)stream,
+                       dout, boxes, dimages, C, H, W, Ho, Wo);
     return lp_check_launch("grid_crop_bwd");
 }

@@ -1,6 +1,6 @@
 """Run-to-run repeatability of the training step inside ONE process: the same model (same seed) and the same batch are stepped twice from
-scratch; every parameter and buffer of the critic is compared bit for bit after each step.  (The critic's arithmetic has no float atomics; the
-generator / encoder gradients pass through the crop-and-resize backward's atomics and may differ in the last bits.)  Used to separate a
+scratch; every parameter and buffer of the critic is compared bit for bit after each step.  (No float atomics remain on the step: the
+crop-and-resize backward is a fixed-order gather, so every tensor should agree bit for bit.)  Used to separate a
 data-parallel exchange problem from nondeterminism of the step itself: scripts/dp_replica_diag.py found replicas whose spectral-norm (u, v)
 buffers differ although their weights are bit-identical.
 usage: python scripts/step_determinism.py [eager|graph] [steps=3] [image_size=128]   (LP_OVERLAP=0 for the one-stream step)"""

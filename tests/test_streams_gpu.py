@@ -1,8 +1,8 @@
 """Concurrent branches (latent_pose_reenactment_amd/streams.py) must not change the result: one eager meta-training iteration (default.yaml
 workload at 128 px: both encoders trained, 6 criterions) from the same initial state, once on ONE stream (LP_OVERLAP=0) and once with the
 pose encoder beside the identity encoder and the VGG criterions beside the discriminator pass, must produce the same losses and the same
-gradients of every parameter -- to the run-to-run spread of the one-stream step itself (the crop-and-resize backward scatters with float
-atomics, like the reference's grid_sample, so two runs differ in the last bits; a missing cross-stream dependency or a tensor re-used
+gradients of every parameter -- to the run-to-run spread of the one-stream step itself (zero since the crop-and-resize backward is a
+fixed-order gather instead of float atomics; a missing cross-stream dependency or a tensor re-used
 while another stream still reads it shows up as an O(1) error).  Also with every optional branch switched on."""
 import os
 import sys

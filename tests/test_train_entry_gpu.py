@@ -48,7 +48,7 @@ def _compare(a_ckpt, a_loss, b_ckpt, b_loss):
 
 
 def test_run_epoch_with_hip_graph_equals_eager(tmp_path):
-    """Two EAGER runs of this loop already differ: float atomics of the crop-and-resize backward add rounding noise, BatchNorm over a
+    """Two EAGER runs of this loop may differ (they did while the crop-and-resize backward used float atomics), BatchNorm over a
     handful of values and Adam (which moves an element whose true gradient is ~0 by +-lr) amplify it.  So the replayed loop is
     held to the eager loop's own run-to-run spread (measured here by a second eager run), on quantities that are smooth in the
     weights: the losses of the LAST iteration -- off at once if a replay saw a stale batch or lost an update -- and each module's
