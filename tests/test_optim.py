@@ -31,7 +31,8 @@ def test_fused_optimizer_matches_plain(kind):
     from latent_pose_reenactment_amd.optim import FusedAdam, FusedRAdam
     from latent_pose_reenactment_amd.utils.radam import RAdam
     torch.manual_seed(1)
-    shapes = [(64, 32, 3, 3), (17,), (5, 7), (1, 512)]
+    # the last three exceed the 1024 x 2048 elements one pass of the capped grid covers (grid-stride loop); 98000 x 512: the label embedding
+    shapes = [(64, 32, 3, 3), (17,), (5, 7), (1, 512), (512, 4608), (2_200_001,), (98000, 512)]
     ps_f = [torch.nn.Parameter(torch.randn(s, device='cuda')) for s in shapes]
     ps_r = [torch.nn.Parameter(p.detach().clone()) for p in ps_f]
     kw = dict(lr=5e-4, betas=(0.0 if kind == 'RAdam' else 0.5, 0.999), eps=1e-5)
@@ -54,14 +55,27 @@ def test_fused_optimizer_matches_plain(kind):
 def test_fused_ema():
     from latent_pose_reenactment_amd.optim import FusedEMA
     torch.manual_seed(2)
-    cur = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.BatchNorm2d(8)).cuda()
-    avg = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.BatchNorm2d(8)).cuda()
-    cur[1].running_mean.normal_(); cur[1].num_batches_tracked.fill_(5)
+    # the Linear (512 x 4608 weight), _Big (2 200 001 parameter and buffer elements) and the 98000 x 512 embedding exceed the 1024 x 2048
+    # elements one pass of the capped grid covers
+    mods = lambda: [torch.nn.Conv2d(3, 8, 3), torch.nn.BatchNorm2d(8), torch.nn.Linear(4608, 512), _Big(2_200_001), torch.nn.Embedding(98000, 512)]
+    cur = torch.nn.Sequential(*mods()).cuda()
+    avg = torch.nn.Sequential(*mods()).cuda()
+    cur[1].running_mean.normal_(); cur[1].num_batches_tracked.fill_(5); cur[3].stat.normal_()
     expect = [a.detach() * 0.972 + c.detach() * (1 - 0.972) for c, a in zip(cur.parameters(), avg.parameters())]
     FusedEMA(cur, avg).update(0.972)
     for a, e in zip(avg.parameters(), expect):
         assert torch.allclose(a, e, rtol=1e-6, atol=1e-7)
     assert torch.equal(avg[1].running_mean, cur[1].running_mean) and int(avg[1].num_batches_tracked) == 5
+    assert torch.equal(avg[3].stat, cur[3].stat)
+
+
+class _Big(torch.nn.Module):
+    """one long odd-length parameter and a float buffer of the same length"""
+
+    def __init__(self, n):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.randn(n))
+        self.register_buffer('stat', torch.zeros(n))
 
 
 @pytest.mark.gpu
