@@ -9,7 +9,12 @@ One "step" = runners/holycow.py:230-257: E -> G -> D x3 -> criterions -> G backw
 every layer of it on the hand-written gfx950 kernels of liblp_hip.so.  N > 1: each rank on its own batch, RCCL gradient all-reduce of
 latent_pose_reenactment_amd.parallel (weak scaling).
 `--workload finetune_step` = BASELINE configs[1] (finetuning-base.yaml; the reference refuses multi-GPU fine-tuning): at N = 1 the
-default run also measures it in a child process and reports it under "finetune_step".
+default `--full` run also measures it in a child process and reports it under "finetune_step".
+
+A plain run does only what the headline needs: set-up, the warm-up and timed steps, `--dump-outputs`, the result line.  `--full` adds the
+side measurements after the timed steps: the live roofline of two instrumented eager steps (`--shapes`), the parity figures quoted from
+profiles/, the drive.py loop, the strict bf16x3 / fp16-option / fine-tuning child runs, the CPU baseline and, at N > 1, the replica check,
+the gradient-exchange diagnosis and the exchange-free single-GPU leg.
 
 Prints ONE JSON line on rank 0, at most 6 KB (see README/DESIGN for the field definitions; ``result_line``): the headline and numbers-only
 side lines.  `--detail FILE` writes the whole record, `--dump-outputs DIR` the arrays of the last timed step."""
@@ -842,14 +847,18 @@ def main():
     ap.add_argument('--workload', default=None, choices=['finetune_step', 'metatrain_step', 'generator'],
                     help='default: metatrain_step for EVERY --gpus value (configs[2], default.yaml: the configuration that is trained data-parallel; one '
                          'workload so that the 1/2/4/8-GPU values form a scaling curve).  finetune_step = BASELINE configs[1] (single GPU in the '
-                         'reference); the default N = 1 run also reports it under "finetune_step"')
+                         'reference); the default N = 1 --full run also reports it under "finetune_step"')
     ap.add_argument('--padding', default='zero', choices=['zero', 'reflection'], help='--gen_padding / --dis_padding of the timed step (the shipped configs and the headline line: zero)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every side measurement (roofline of instrumented eager steps, parity figures, drive '
+                         'loop, strict bf16x3 / fp16-option / fine-tuning child runs, CPU baseline; N > 1: replica check, exchange diagnosis, '
+                         'single-GPU leg).  Default: set-up, warm-up, timed steps, --dump-outputs and the result line only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline leg')
     ap.add_argument('--cpu-baseline-only', action='store_true', help='only the CPU baseline leg (no GPU work): prints its JSON object')
-    ap.add_argument('--no-also', action='store_true', help='skip the side measurements (strict bf16x3 mode, fine-tuning step)')
-    ap.add_argument('--no-drive', action='store_true', help='skip the drive.py frame-loop measurement (PMC passes: keeps the launch population to the step)')
+    ap.add_argument('--no-also', action='store_true', help='--full without the child runs (strict bf16x3 mode, fp16 option, fine-tuning step)')
+    ap.add_argument('--no-drive', action='store_true', help='--full without the drive.py frame-loop measurement (PMC passes: keeps the launch population to the step)')
     ap.add_argument('--eager', action='store_true', help='do not capture the step into hipGraphs')
-    ap.add_argument('--shapes', default=None, help='write the per-shape conv / wgrad timing table of the instrumented steps (CSV)')
+    ap.add_argument('--shapes', default=None, help='with --full: write the per-shape conv / wgrad timing table of the instrumented steps (CSV)')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL; gloo only for functional tests)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='after the timed steps, write what the timed step returned in its LAST step (training step: all_data, losses_G, '
@@ -863,6 +872,8 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error('--steps must be >= 1')
+    if a.shapes and not a.full:
+        ap.error('--shapes needs --full (the table comes from its instrumented steps)')
     if a.cpu_worker:
         return cpu_worker(a.cpu_worker)
     if a.cpu_baseline_only:
@@ -952,27 +963,29 @@ def main():
         sampled = sum(1 for shape, n in written.values() if n != int(torch.Size(shape).numel()))
         print(f'[bench] --dump-outputs: {len(written)} arrays ({sampled} sampled) of step {a.steps} of {a.steps} -> {a.dump_outputs}', file=sys.stderr)
     last = None
-    # Live per-kernel timing for the roofline entry: HIP events recorded on the launch stream around every conv launch.
-    # Graph replays cannot carry per-kernel events, so the instrumented steps run eagerly right after the timed region
-    # (same process, same buffers, same kernels); they are not part of `value`.
-    # They run on ONE stream (LP_OVERLAP=0): beside a concurrent branch (streams.py) a kernel's event span would include the time it shares
-    # the CUs with another stream's kernels, which is not what a per-kernel roofline states.
-    hipops.PROFILE = []
-    inst = eager_step if a.workload != 'generator' else step
-    keep_overlap = os.environ.get('LP_OVERLAP')
-    os.environ['LP_OVERLAP'] = '0'
-    try:
-        for _ in range(2):
-            inst()
-        torch.cuda.synchronize()
-    finally:
-        if keep_overlap is None:
-            os.environ.pop('LP_OVERLAP', None)
-        else:
-            os.environ['LP_OVERLAP'] = keep_overlap
-    prof, hipops.PROFILE = hipops.PROFILE, None
+    prof = []
+    if a.full:
+        # Live per-kernel timing for the roofline entry: HIP events recorded on the launch stream around every conv launch.
+        # Graph replays cannot carry per-kernel events, so the instrumented steps run eagerly right after the timed region
+        # (same process, same buffers, same kernels); they are not part of `value`.
+        # They run on ONE stream (LP_OVERLAP=0): beside a concurrent branch (streams.py) a kernel's event span would include the time it shares
+        # the CUs with another stream's kernels, which is not what a per-kernel roofline states.
+        hipops.PROFILE = []
+        inst = eager_step if a.workload != 'generator' else step
+        keep_overlap = os.environ.get('LP_OVERLAP')
+        os.environ['LP_OVERLAP'] = '0'
+        try:
+            for _ in range(2):
+                inst()
+            torch.cuda.synchronize()
+        finally:
+            if keep_overlap is None:
+                os.environ.pop('LP_OVERLAP', None)
+            else:
+                os.environ['LP_OVERLAP'] = keep_overlap
+        prof, hipops.PROFILE = hipops.PROFILE, None
     replicas = None
-    if world > 1 and a.workload != 'generator':
+    if a.full and world > 1 and a.workload != 'generator':
         # data-parallel invariant (apex Reducer semantics, train.py:196-200): after any number of steps every rank holds bit-identical parameters
         # (same start by broadcast, same averaged gradients, same optimizer arithmetic).  Checked on the parameters' BIT patterns: two int64
         # checksums per rank, MIN and MAX over ranks must agree.
@@ -997,7 +1010,7 @@ def main():
                         'note': 'checked after the warm-up, timed and instrumented steps, BEFORE the exchange-free single-GPU leg (which lets the ranks drift apart on purpose)'}
 
     comm = None
-    if world > 1 and a.workload != 'generator' and getattr(tm, 'reducer', None) is not None:
+    if a.full and world > 1 and a.workload != 'generator' and getattr(tm, 'reducer', None) is not None:
         # diagnosis of the gradient exchange: a few more steps of the SAME step function with events around every
         # all-reduce issue and around the wait of its consumer -- per-bucket bytes, how long each collective had to finish behind other work,
         # and how long the compute stream still stood in the wait (exposed_comm_ms_per_step).  Outside the timed region.
@@ -1022,7 +1035,7 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-        if a.workload != 'generator':
+        if a.full and a.workload != 'generator':
             # the N = 1 point of THIS workload measured inside the same job (a cross-check of the driver's separate --gpus 1 run):
             # every rank repeats the timed loop with the gradient exchange removed -- one GPU's throughput on the same step and batch
             red, tm.reducer = tm.reducer, None
@@ -1177,7 +1190,7 @@ def main():
                                         'frac_of_bf16_peak': round(tf / (dt / a.steps) / (MFMA_BF16_PEAK_TFLOPS * world), 4),
                                         'note': 'useful dense 2*MAC of one step as executed (step_algorithmic_tflop) / ms_per_step / (2.5 PF x n_gpus)'}
         out.update(extra)
-        if a.workload != 'generator':
+        if a.full and a.workload != 'generator':
             out['parity'] = measured_parity('default' if a.prec == 'f16' and not os.environ.get('LP_PREC_E') else a.prec, a.workload)
         if solo is not None:
             out['single_gpu_same_workload'] = solo
@@ -1185,7 +1198,7 @@ def main():
             out['replicas'] = replicas
         if comm is not None:
             out['gradient_exchange'] = comm
-        if world == 1 and not a.no_drive:
+        if a.full and world == 1 and not a.no_drive:
             try:
                 out['drive'] = drive_fps(args)
                 out['drive']['batch_8'] = {k: v for k, v in drive_fps(args, frames=30, batch=8).items() if k != 'note'}
@@ -1198,7 +1211,7 @@ def main():
             fd, detail = tempfile.mkstemp(suffix='.json', prefix='bench_child_')
             os.close(fd)
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-also',
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '20', '--warmup', '5', '--full', '--no-cpu-baseline', '--no-also',
                                     '--detail', detail] + extra_args, capture_output=True, text=True, timeout=timeout, env=env)
                 if os.path.getsize(detail) == 0:
                     raise RuntimeError(f'child exited with {r.returncode} before its result: {r.stderr[-500:]}')
@@ -1206,7 +1219,7 @@ def main():
                     return json.load(f)
             finally:
                 os.unlink(detail)
-        if world == 1 and a.prec == 'f16' and a.workload in ('finetune_step', 'metatrain_step') and not a.no_also:
+        if a.full and world == 1 and a.prec == 'f16' and a.workload in ('finetune_step', 'metatrain_step') and not a.no_also:
             # the strict-parity mode (bf16x3: 3 MFMAs per MAC, fp32-class results) of the SAME workload, measured by the same script in a
             # child process.  Parity status of the two modes: the f16 headline meets the 1e-3 OUTPUT gate of BASELINE.json; the full
             # SURVEY 8(d) gate (outputs, losses AND every parameter gradient within 1e-3) is met in bf16x3 only.
@@ -1217,7 +1230,7 @@ def main():
                                              'parity': measured_parity('bf16x3', a.workload)}
             except Exception as ex:
                 out['strict_mode_bf16x3'] = {'error': repr(ex)}
-        if world == 1 and a.prec == 'f16' and a.workload in ('finetune_step', 'metatrain_step') and not a.no_also \
+        if a.full and world == 1 and a.prec == 'f16' and a.workload in ('finetune_step', 'metatrain_step') and not a.no_also \
                 and not (os.environ.get('LP_PREC_G') or os.environ.get('LP_D_DPASS_PREC')):
             # round 5's assignment (fp16 operands in the generator and in the critic's D-side passes) of the same workload: faster, meets the 1e-3 gate
             # on every forward quantity and loss but NOT on the parameter gradients (generator 1.0 - 1.7e-3, critic <= 9.3e-3 tie-masked) -- an option
@@ -1231,7 +1244,7 @@ def main():
                             '`discriminator_f16_operands` entries of profiles/' + ROUND + '_parity_gradients_f16.json'}
             except Exception as ex:
                 out['fp16_generator_and_critic_option'] = {'error': repr(ex)}
-        if world == 1 and default_run and not a.no_also:
+        if a.full and world == 1 and default_run and not a.no_also:
             # BASELINE configs[1] (fine-tuning step, single GPU in the reference) beside the scaling workload
             try:
                 j = child(['--prec', a.prec, '--workload', 'finetune_step'])
@@ -1239,7 +1252,7 @@ def main():
                 out['finetune_step']['config'] = j.get('config')
             except Exception as ex:
                 out['finetune_step'] = {'error': repr(ex)}
-        if world == 1 and not a.no_cpu_baseline and a.workload != 'generator':
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload != 'generator':
             try:
                 out['cpu_baseline'] = cpu_baseline(args, full=a.cpu_baseline_full, workload=a.workload)
             except Exception as ex:      # never lose the GPU line because of the baseline leg

@@ -1,5 +1,5 @@
 """3x3 dense conv family INSIDE a captured step: kernel durations from a one-step rocprofv3 breakdown (scripts/step_breakdown.py) against the
-algorithmic FLOPs of the same launches (bench.py --shapes table, kind conv_igemm, two instrumented steps) -> the in-graph roofline figure
+algorithmic FLOPs of the same launches (bench.py --full --shapes table, kind conv_igemm, two instrumented steps) -> the in-graph roofline figure
 that bench.py prints beside its live eager-event one.
 usage: python scripts/in_graph_conv.py <step_breakdown.csv> <conv_shapes.csv> > profiles/r06_conv3x3_in_graph.json
 Family = conv_pipe_kernel (all variants) + conv_dma_kernel<3, ...> and <2, ...> (the phase forms of the x2-upsampled convs, round 6) except the instantiations whose last template flag (GH) is true -- the identity

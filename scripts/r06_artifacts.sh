@@ -19,8 +19,8 @@ grep -E "passed|failed|error" $O/${R}_pytest_gpu.log | tail -3 | cut -c1-300 | t
 grep -E "^\[parity|^\[e1|^\[replicas" $O/${R}_pytest_gpu.log | cut -c1-1500 > $O/${R}_parity_lines.txt
 cp $O/${R}_parity_configs2_*.json $O/${R}_parity_gradients_*.json profiles/ 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${R}_smoke.txt 2>&1; echo "smoke rc=$?" | tee -a $O/summary.txt
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-drive --shapes $O/${R}_conv_shapes_metatrain.csv > $O/${R}_bench_quick.json 2> $O/${R}_bench_quick.err; echo "quick bench rc=$?" | tee -a $O/summary.txt
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_prof_meta -o ${R} -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-drive > $O/${R}_prof_meta.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-drive --shapes $O/${R}_conv_shapes_metatrain.csv > $O/${R}_bench_quick.json 2> $O/${R}_bench_quick.err; echo "quick bench rc=$?" | tee -a $O/summary.txt
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_prof_meta -o ${R} -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-drive > $O/${R}_prof_meta.log 2>&1
 python scripts/step_breakdown.py $O/${R}_prof_meta/${R}_kernel_trace.csv > $O/${R}_step_breakdown_metatrain.csv 2>> $O/${R}_prof_meta.log
 cp $O/${R}_prof_meta/${R}_kernel_stats.csv $O/${R}_metatrain_step_kernel_stats.csv 2>/dev/null
 rm -f $O/${R}_prof_meta/${R}_kernel_trace.csv
@@ -29,7 +29,7 @@ cp $O/${R}_conv3x3_in_graph.json profiles/ 2>/dev/null
 FAM="conv_pipe_kernel|conv_dma_kernel|conv_wgrad_kernel|wgrad3_pipe_kernel|wgrad1x1_kernel|bn_bwd16"
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_WAVE_CYCLES"; do
   tag=$(echo $c | tr ' ' '+')
-  timeout 400 rocprofv3 --pmc $c --kernel-trace --kernel-include-regex "$FAM" --output-format csv -d $O/${R}_pmc_$tag -o ${R} -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-also --no-drive > $O/${R}_pmc_$tag.log 2>&1
+  timeout 400 rocprofv3 --pmc $c --kernel-trace --kernel-include-regex "$FAM" --output-format csv -d $O/${R}_pmc_$tag -o ${R} -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-also --no-drive > $O/${R}_pmc_$tag.log 2>&1
   echo "pmc $tag rc=$?" >> $O/summary.txt
   rm -f $O/${R}_pmc_$tag/${R}_kernel_trace.csv
 done
@@ -42,17 +42,17 @@ python scripts/pmc_summary.py --json "bn_bwd16" $O/${R}_pmc_*/*counter_collectio
 python scripts/pmc_summary.py $O/${R}_pmc_*/*counter_collection.csv > $O/${R}_pmc_metatrain_step.csv 2>> $O/${R}_pmc_summary.err
 rm -rf $O/${R}_pmc_*/
 cp $O/${R}_pmc_conv3x3_metatrain.json profiles/ 2>/dev/null
-timeout 1800 python bench.py --shapes $O/${R}_conv_shapes_metatrain.csv > $O/${R}_bench.json 2> $O/${R}_bench.err; echo "bench rc=$?" | tee -a $O/summary.txt
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_prof_ft -o ${R} -- python bench.py --workload finetune_step --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-drive > $O/${R}_prof_ft.log 2>&1
+timeout 1800 python bench.py --full --shapes $O/${R}_conv_shapes_metatrain.csv > $O/${R}_bench.json 2> $O/${R}_bench.err; echo "bench rc=$?" | tee -a $O/summary.txt
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_prof_ft -o ${R} -- python bench.py --full --workload finetune_step --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-drive > $O/${R}_prof_ft.log 2>&1
 python scripts/step_breakdown.py $O/${R}_prof_ft/${R}_kernel_trace.csv > $O/${R}_step_breakdown_finetune.csv 2>> $O/${R}_prof_ft.log
 cp $O/${R}_prof_ft/${R}_kernel_stats.csv $O/${R}_finetune_step_kernel_stats.csv 2>/dev/null
 rm -rf $O/${R}_prof_ft $O/${R}_prof_meta
-timeout 300 python bench.py --workload generator --generator FSTH_plus --image_size 512 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_fsthplus512.json 2> $O/${R}_bench_fsthplus512.err
-timeout 300 python bench.py --workload generator --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_generator.json 2> $O/${R}_bench_generator.err
-LP_PREC_G=f16 timeout 300 python bench.py --workload generator --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_generator_f16.json 2> $O/${R}_bench_generator_f16.err
-LP_OVERLAP=0 timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_one_stream.json 2> $O/${R}_bench_one_stream.err
-LP_OVERLAP=0 timeout 300 python bench.py --workload finetune_step --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_finetune_one_stream.json 2> $O/${R}_bench_finetune_one_stream.err
-env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout 600 python bench.py --gpus 2 --steps 6 --warmup 2 --backend gloo --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_dp2_gloo_one_gpu_functional.json 2> $O/${R}_bench_dp2.err
+timeout 300 python bench.py --full --workload generator --generator FSTH_plus --image_size 512 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_fsthplus512.json 2> $O/${R}_bench_fsthplus512.err
+timeout 300 python bench.py --full --workload generator --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_generator.json 2> $O/${R}_bench_generator.err
+LP_PREC_G=f16 timeout 300 python bench.py --full --workload generator --steps 20 --warmup 5 --no-cpu-baseline > $O/${R}_bench_generator_f16.json 2> $O/${R}_bench_generator_f16.err
+LP_OVERLAP=0 timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_one_stream.json 2> $O/${R}_bench_one_stream.err
+LP_OVERLAP=0 timeout 300 python bench.py --full --workload finetune_step --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_finetune_one_stream.json 2> $O/${R}_bench_finetune_one_stream.err
+env -u WORLD_SIZE -u RANK -u LOCAL_RANK timeout 600 python bench.py --full --gpus 2 --steps 6 --warmup 2 --backend gloo --no-cpu-baseline --no-also --no-drive > $O/${R}_bench_dp2_gloo_one_gpu_functional.json 2> $O/${R}_bench_dp2.err
 PREC=1 WHAT=conv timeout 200 python scripts/conv_micro.py 2>&1 | grep prec > $O/${R}_conv_micro_bf16x3.txt
 PREC=2 WHAT=conv timeout 200 python scripts/conv_micro.py 2>&1 | grep prec > $O/${R}_conv_micro_f16.txt
 (echo "# round 6: the generator's x2-upsampled 3x3 convs (N = 8), fused-upsample kernels vs the phase-decomposed forms (scripts/r06/phase_micro.py; prec 1 = bf16x3, 2 = f16; dense count = the conv as the reference executes it)"; for pr in 1 2; do PREC=$pr timeout 200 python scripts/r06/phase_micro.py 2>&1 | grep prec; done) > $O/${R}_phase_conv.txt

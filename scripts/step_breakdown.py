@@ -1,4 +1,4 @@
-"""Per-step kernel breakdown from a rocprofv3 kernel trace of bench.py: picks one steady-state hipGraph replay of the
+"""Per-step kernel breakdown from a rocprofv3 kernel trace of bench.py --full: picks one steady-state hipGraph replay of the
 fine-tuning step (delimited by the mt_step_inc_kernel launches: one per optimizer step, G then D) and prints kernel
 family, launches, total ms -- plus the GPU idle time inside the step.
 usage: python scripts/step_breakdown.py <kernel_trace.csv> > breakdown.csv"""
@@ -17,7 +17,7 @@ if len(marks) < 26:
 # a step holds 2 markers (G, D) -- 3 when the generator's slice of optimizer_G is stepped on its own (round 6: the early updates beside the
 # encoders' backward) -- so the period is read off the trace: the smallest p for which the kernel counts between consecutive markers repeat
 # with period p over the last replays.  A step = from one marker to the p-th next; take the 4th-from-last full step (inside the timed replays)
-marks = marks[:-6]          # (bench.py ends with two EAGER instrumented steps -- the live roofline figure: up to 6 markers that are not graph replays)
+marks = marks[:-6]          # (a bench.py --full run ends with two EAGER instrumented steps -- the live roofline figure: up to 6 markers that are not graph replays)
 gaps = [marks[i + 1] - marks[i] for i in range(len(marks) - 1)]
 def close(x, y):          # (kernels of concurrent streams interleave a little differently from replay to replay)
     return abs(x - y) <= max(4, 0.03 * max(x, y))

@@ -15,7 +15,7 @@ rows.sort()
 marks = [i for i, r in enumerate(rows) if 'mt_step_inc' in r[2]]
 if len(marks) < 14:
     sys.exit('not enough optimizer steps in the trace')
-a, b = marks[-9], marks[-7]          # the step scripts/step_breakdown.py cuts (the last two steps of a bench.py trace are its eager one-stream instrumented steps)
+a, b = marks[-9], marks[-7]          # the step scripts/step_breakdown.py cuts (the last two steps of a bench.py --full trace are its eager one-stream instrumented steps)
 seg = rows[a:b]
 t0, t1 = seg[0][0], max(e for _, e, *_ in seg)
 ev = []

@@ -73,7 +73,7 @@ def test_bench_starts_its_own_ranks_from_plain_python():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
-                        '--image_size', '128', '--no-cpu-baseline', '--no-also', '--no-drive'], env=env, cwd=ROOT, capture_output=True,
+                        '--image_size', '128', '--full', '--no-cpu-baseline', '--no-also', '--no-drive'], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -94,7 +94,7 @@ def test_bench_two_gpus_over_rccl_keeps_replicas_bit_identical():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'nccl', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-also', '--no-drive'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
+                        '--full', '--no-cpu-baseline', '--no-also', '--no-drive'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
