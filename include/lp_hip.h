@@ -440,6 +440,33 @@ int lp_reduce_hinge_bwd(const float* real, const float* fake_d, const float* gra
 int lp_proj_score_fwd(const float* out, const float* embed, float* pooled, float* dot, int N, int HW, int C, void* stream);
 int lp_proj_score_bwd(const float* out, const float* embed, const float* pooled, const float* g_pooled, const float* g_dot, float* d_out,
                       float* d_embed, int N, int HW, int C, void* stream);
+/* Tail of the conv embedders (embedders/FSTH.py, embedders/no_pose_encoder.py): out [B*K][HW][C] = pre-activation output of the last down block.
+ * lp_embed_tail_fwd: elem[b*K+k][c] = sum_hw relu(out), embeds[b][c] = mean_k (is_max 0) | max_k (is_max 1; argk [B][C] receives the FIRST frame that
+ * attains it) in one launch.  lp_embed_tail_bwd: d_out = [out > 0] (g_elem + g_embeds / K | g_embeds [k == argk]); g_elem / g_embeds | NULL = zero. */
+int lp_embed_tail_fwd(const float* out, float* elem, float* embeds, int* argk, int B, int K, int HW, int C, int is_max, void* stream);
+int lp_embed_tail_bwd(const float* out, const float* g_elem, const float* g_embeds, const int* argk, float* d_out, int B, int K, int HW, int C,
+                      int is_max, void* stream);
+/* First layer of the stickman-conditioned nets: conv 3x3 (zero padding) | 1x1 from 5..8 input channels to Cout % 64 == 0 whose input is the channel
+ * concatenation of TWO fp32 tensors, never materialised (csrc/conv_stem8.hip).  Source s in {a, b}: pointer (NULL: unused), stride_s = 4 element
+ * strides (image, channel, row, column -- NCHW, NHWC or a view), Cs channels.  cmap: nibble c = (source << 3) | channel in that source for conv
+ * input channel c (source 0 = a, 1 = b), e.g. a,a,a,b,b,b (concatenated) or a,b,a,b,a,b (interleaved).  lp_stem8_supported: W % 16 == 0 and rows
+ * that fit LDS (one answer for all operand modes and for forward + weight gradient).
+ *   lp_stem8_fwd    y [N][H][W][Cout] (|NULL) = alpha * conv + bias on the matrix cores in operand mode prec (weight pack [tap][CoutP][CinP] from
+ *                   lp_pack_weights mode 0; bf16x3: hi + lo) and / or out_hi (, out_lo) = the operand planes of (out_relu ? relu(y) : y),
+ *                   bit-identical to lp_act_pack of y.
+ *   lp_stem8_wgrad  dw [Cout][Cin][k*k] and dbias [Cout] (|NULL) from fp32 dy [N][H][W][Cout]; fp32, fixed summation order;
+ *                   workspace of lp_stem8_wgrad_workspace_bytes.
+ *   lp_stem8_dgrad  dx (strides stride_dx, Cb <= 4 channels) = the gradient w.r.t. source b (the image) only: alpha * conv^T(dy, w) with
+ *                   w = fp32 W_orig [Cout][Cin][k*k]; fp32. */
+int lp_stem8_supported(int Cin, int Cout, int ksize, int W);
+int lp_stem8_fwd(const float* xa, const long long* stride_a, int Ca, const float* xb, const long long* stride_b, int Cb, int cmap,
+                 const uint16_t* w_hi, const uint16_t* w_lo, float* y, const float* bias, const float* alpha, int N, int H, int W, int Cin,
+                 int Cout, int CinP, int CoutP, int ksize, int prec, uint16_t* out_hi, uint16_t* out_lo, int out_relu, void* stream);
+long long lp_stem8_wgrad_workspace_bytes(int N, int H, int Cout, int ksize);
+int lp_stem8_wgrad(const float* xa, const long long* stride_a, int Ca, const float* xb, const long long* stride_b, int Cb, int cmap,
+                   const float* dy, float* dw, float* dbias, float* workspace, int N, int H, int W, int Cin, int Cout, int ksize, void* stream);
+int lp_stem8_dgrad(const float* dy, const float* w, const float* alpha, float* dx, const long long* stride_dx, int Cb, int cmap, int N, int H,
+                   int W, int Cin, int Cout, int ksize, void* stream);
 /* (ABI 11, round 6) Input side of the VGG criterions (criterions/common/perceptual_loss.py:72-80,86-93): x NCHW [N][3][HW] in [-1, 1] ->
  * out NHWC [N][HW][3] = ((x + 1) / 2 - mean[c]) / std[c] (mean, std: 3 device floats), the reference's operations in the reference's order;
  * lp_image_prep_bwd: dx NCHW = g NHWC / std[c] / 2. */

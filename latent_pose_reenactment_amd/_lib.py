@@ -98,6 +98,13 @@ SIGNATURES = {
     'lp_sum2x2_planes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'lp_proj_score_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'lp_proj_score_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'lp_embed_tail_fwd': (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    'lp_embed_tail_bwd': (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    'lp_stem8_supported': (_i, [_i] * 4),
+    'lp_stem8_fwd': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 5 + [_i] * 9 + [_vp, _vp, _i, _vp]),
+    'lp_stem8_wgrad_workspace_bytes': (_ll, [_i] * 4),
+    'lp_stem8_wgrad': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 4 + [_i] * 6 + [_vp]),
+    'lp_stem8_dgrad': (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     'lp_image_prep_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'lp_image_prep_bwd': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'lp_pool_grad_pack': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

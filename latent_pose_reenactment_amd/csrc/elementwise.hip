@@ -1271,6 +1271,70 @@ extern "C" int lp_proj_score_bwd(const float* out, const float* embed, const flo
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Tail of the conv embedders (embedders/FSTH.py:82-92 of the reference): out = relu(out); embeds_elemwise[b,k,c] = sum_hw out; embeds[b,c] = mean
+// or max over the K frames -- one launch forward, one backward.  out [B*K][HW][C] is the pre-activation output of the last down block.  A workgroup
+// takes one identity x 64 channels; wave w sums the frames k = w, w+4, ...; the frames are combined in a fixed order (max: the FIRST frame that attains
+// the maximum gets the gradient, as torch.max does; ties only occur at exactly 0, where the ReLU blocks the gradient anyway).
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void embed_tail_fwd_kernel(const float* __restrict__ out, float* __restrict__ elem, float* __restrict__ embeds,
+                                                             int* __restrict__ argk, int K, int HW, int C, int is_max) {
+    __shared__ float sv[4][64];
+    __shared__ int sk[4][64];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = blockIdx.y * 64 + lane;
+    float best = 0.f;
+    int bk = -1;
+    if (c < C)
+        for (int k = w; k < K; k += 4) {
+            const float* src = out + ((size_t)(b * K + k) * HW) * C + c;
+            float s = 0.f;
+            for (int p = 0; p < HW; ++p) s += fmaxf(src[(size_t)p * C], 0.f);
+            elem[(size_t)(b * K + k) * C + c] = s;
+            if (!is_max) best += s;
+            else if (bk < 0 || s > best) { best = s; bk = k; }
+        }
+    sv[w][lane] = best; sk[w][lane] = bk;
+    __syncthreads();
+    if (w == 0 && c < C) {
+        if (!is_max) { embeds[(size_t)b * C + c] = ((sv[0][lane] + sv[1][lane]) + (sv[2][lane] + sv[3][lane])) / (float)K; return; }
+        float m = sv[0][lane];
+        int mk = sk[0][lane];
+        for (int j = 1; j < 4; ++j) {
+            const float v = sv[j][lane];
+            const int vk = sk[j][lane];
+            if (vk >= 0 && (mk < 0 || v > m || (v == m && vk < mk))) { m = v; mk = vk; }
+        }
+        embeds[(size_t)b * C + c] = m;
+        argk[(size_t)b * C + c] = mk;
+    }
+}
+__global__ __launch_bounds__(256) void embed_tail_bwd_kernel(const float* __restrict__ out, const float* __restrict__ g_elem, const float* __restrict__ g_embeds,
+                                                             const int* __restrict__ argk, float* __restrict__ d_out, int K, int HW, int C, int is_max) {
+    const int bk = blockIdx.x, b = bk / K, k = bk - b * K;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float g = g_elem ? g_elem[(size_t)bk * C + c] : 0.f;
+        if (g_embeds) {
+            const float ge = g_embeds[(size_t)b * C + c];
+            if (!is_max) g += ge / (float)K;
+            else if (argk[(size_t)b * C + c] == k) g += ge;
+        }
+        for (int p = 0; p < HW; ++p) { const size_t i = ((size_t)bk * HW + p) * C + c; d_out[i] = out[i] > 0.f ? g : 0.f; }
+    }
+}
+extern "C" int lp_embed_tail_fwd(const float* out, float* elem, float* embeds, int* argk, int B, int K, int HW, int C, int is_max, void* stream) {
+    if (!out || !elem || !embeds || (is_max && !argk)) return lp_set_error(LP_ERR_ARG, "lp_embed_tail_fwd: null pointer");
+    if (B < 1 || K < 1 || HW < 1 || C < 1) return lp_set_error(LP_ERR_ARG, "lp_embed_tail_fwd: empty tensor");
+    hipLaunchKernelGGL(embed_tail_fwd_kernel, dim3(B, (C + 63) / 64), dim3(256), 0, (hipStream_t)stream, out, elem, embeds, argk, K, HW, C, is_max);
+    return lp_check_launch("embed_tail_fwd");
+}
+extern "C" int lp_embed_tail_bwd(const float* out, const float* g_elem, const float* g_embeds, const int* argk, float* d_out, int B, int K, int HW,
+                                 int C, int is_max, void* stream) {
+    if (!out || !d_out || (is_max && g_embeds && !argk)) return lp_set_error(LP_ERR_ARG, "lp_embed_tail_bwd: null pointer");
+    if (B < 1 || K < 1 || HW < 1 || C < 1) return lp_set_error(LP_ERR_ARG, "lp_embed_tail_bwd: empty tensor");
+    hipLaunchKernelGGL(embed_tail_bwd_kernel, dim3(B * K), dim3(256), 0, (hipStream_t)stream, out, g_elem, g_embeds, argk, d_out, K, HW, C, is_max);
+    return lp_check_launch("embed_tail_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Input side of the VGG criterions (criterions/common/perceptual_loss.py:72-80,86-93 of the reference): x in [-1, 1], NCHW [N][3][HW] ->
 // ((x + 1) / 2 - mean[c]) / std[c] as NHWC [N][HW][3] -- the same fp32 operations in the same order, and the layout change, in one launch
 // (round 6: add + div + sub + div + the NCHW -> NHWC copy were five launches per image batch); backward dx[n,c,p] = g[n,p,c] / std[c] / 2.

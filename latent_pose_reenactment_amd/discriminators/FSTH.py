@@ -1,0 +1,48 @@
+"""Stickman-conditioned projection discriminator (reference API: discriminators/FSTH.py:11-172), key-compatible state_dict.
+
+The critic of discriminators/no_landmarks.py -- same blocks, three passes, ``prepare_step`` / ``start_real_pass``, per-pass operand modes,
+``keep_reference_waste`` and ``enable_finetuning``, all inherited -- behind a stem that sees the target pose drawn as a stickman next to the image:
+  * the stem's convs take in_channels + out_channels (6) channels and, unlike no_landmarks, keep their ``padding(1)`` modules, so their state-dict
+    keys are ``down_block.1.*`` / ``down_block.4.*``;
+  * the reference concatenates the 4-D tensors on dim 2 (rows) and views the result as b x 6 x h x w (FSTH.py:153-158): stickman and image planes
+    end up INTERLEAVED over the channels (s0, r0, s1, r1, s2, r2) -- ``fsth.interleaved_order``;
+  * the stickman is a constant for autograd and is shared by the fake and the real passes; pass 2 sees the detached image (inherited).
+``--dis_padding reflection`` would also reflect-pad the stem here; it is refused at construction instead of being run with zero padding."""
+from latent_pose_reenactment_amd.discriminators import no_landmarks as _base
+from latent_pose_reenactment_amd.fsth import TwoSourceStem, interleaved_order, refuse_reflection
+
+
+class Wrapper(_base.Wrapper):
+    @staticmethod
+    def get_net(args):
+        return Discriminator(args.dis_padding, args.in_channels, args.out_channels, args.num_channels, args.max_num_channels,
+                             args.embed_channels, args.dis_num_blocks, args.image_size, args.num_labels).to(args.device)
+
+
+class Discriminator(TwoSourceStem, _base.Discriminator):
+    CHANNEL_ORDER = staticmethod(interleaved_order)
+
+    def __init__(self, padding, in_channels, out_channels, num_channels, max_num_channels, embed_channels, dis_num_blocks,
+                 image_size, num_labels):
+        refuse_reflection(padding, '--dis_padding')
+        super().__init__(padding, in_channels + out_channels, out_channels, num_channels, max_num_channels, embed_channels, dis_num_blocks,
+                         image_size, num_labels)
+
+    def _take_stick(self, data_dict):
+        stick = data_dict['dec_stickmen']
+        if stick.dim() > 4:
+            stick = stick[:, 0]
+        self._set_stick(stick)
+
+    def start_real_pass(self, data_dict):
+        if data_dict.get('dec_stickmen') is None:
+            return
+        self._take_stick(data_dict)
+        super().start_real_pass(data_dict)
+
+    def forward(self, data_dict):
+        self._take_stick(data_dict)
+        try:
+            super().forward(data_dict)
+        finally:
+            self._set_stick(None)

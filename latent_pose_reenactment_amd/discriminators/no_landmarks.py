@@ -134,7 +134,9 @@ class _DisBlock(nn.Module):
                 return AvgPool2Fn.apply(out, False)
             return pool_relu(out, next_prec) if self.downsample else out
         h, h16 = _conv(x_relu, c1, track, states, prec, ksize=3, x16=xr16, emit16=1, want_y=not PLANES_ONLY)      # (h itself is never read: conv2 takes the planes)
-        if self.downsample and CONV_POOL:
+        # (the skip conv on the POOLED input needs a map the weight-gradient kernel covers, W >= 4: a block that pools 4 x 4 -> 2 x 2 -- the last
+        #  block of the toy conv embedders -- keeps its skip conv at full resolution, i.e. the unfused form below; no shipped geometry gets there)
+        if self.downsample and CONV_POOL and x_relu.shape[2] >= 8:
             # pool(conv2(relu(h)) + skip(x)) = conv4x4/2(relu(h)) + skip(pool(x)): the 1x1 skip conv commutes with the average
             xp = AvgPool2Fn.apply(x_relu, False)
             shortcut_lo = _conv(xp, self.skip._modules['0'], track, states, prec, ksize=1) if self.has_skip else xp
@@ -161,52 +163,51 @@ def pool_relu(out, next_prec):
     return y, o16
 
 
-class Discriminator(nn.Module):
-    def __init__(self, padding, in_channels, out_channels, num_channels, max_num_channels, embed_channels, dis_num_blocks,
-                 image_size, num_labels):
-        super().__init__()
-        if padding not in ('zero', 'reflection'):
-            raise Exception('Incorrect `padding` argument, required `zero` or `reflection`')       # (no_landmarks.py:49-50)
-        reflect = padding == 'reflection'          # (the stem's convs keep their zero padding: no_landmarks.py:52-60 has `padding(1)` commented out)
-        self.out_channels = embed_channels
-        self.down_block = _Indexed(_0=SNWeight((num_channels, in_channels, 3, 3), True, SN_EPS_CONV),
-                                   _2=SNWeight((num_channels, num_channels, 3, 3), True, SN_EPS_CONV))
+class ResTrunk(nn.Module):
+    """stem (conv3x3 -> ReLU -> conv3x3 -> AvgPool2d + 1x1 skip) and norm-'none' ResBlocks shared by the critics and the conv embedders of the FSTH
+    family: parameters ``down_block`` / ``skip`` (built by ``_build_stem``) and a ModuleList ``blocks`` of ``_DisBlock``; the per-step weight packs,
+    the batched power iteration and the forward through stem + blocks live here, heads and passes in the subclasses"""
+    # positions of the stem's two convs inside ``down_block`` (the state-dict keys): no_landmarks.py:52-60 has its `padding(1)` entries commented
+    # out; the FSTH family (discriminators/FSTH.py, embedders/FSTH.py) keeps them -> ('1', '4')
+    STEM_KEYS = ('0', '2')
+
+    def _strict_modes(self):
+        """(operand mode, first unit) of every pass that may leave the default mode: the weight packs of those modes are made ahead"""
+        return ()
+
+    def _head_layers(self):
+        """spectrally normalised layers behind the blocks that share the batched power iteration"""
+        return []
+
+    def _base_prec(self):
+        """operand mode of the units no pass runs strict (the mode the full set of weight packs is made in)"""
+        return default_prec()
+
+    def _build_stem(self, in_channels, num_channels):
+        k0, k2 = self.STEM_KEYS
+        self.down_block = _Indexed(**{'_' + k0: SNWeight((num_channels, in_channels, 3, 3), True, SN_EPS_CONV),
+                                      '_' + k2: SNWeight((num_channels, num_channels, 3, 3), True, SN_EPS_CONV)})
         self.skip = _Indexed(_0=SNWeight((num_channels, in_channels, 1, 1), True, SN_EPS_CONV))
-        self.blocks = nn.ModuleList()
-        num_down = min(int(math.log(image_size, 2)) - 2, dis_num_blocks)
-        cin = num_channels
-        cout = cin
-        for i in range(1, num_down):
-            cout = min(cin * 2, max_num_channels)
-            if i == dis_num_blocks - 1:
-                cout = self.out_channels
-            self.blocks.append(_DisBlock(cin, cout, True, reflect))
-            cin = cout
-        for i in range(num_down, dis_num_blocks):
-            if i == dis_num_blocks - 1:
-                cout = self.out_channels
-            self.blocks.append(_DisBlock(cin, cout, False, reflect))
-        self.linear = SNWeight((1, self.out_channels), True, SN_EPS_CONV)
-        self.embed = SNWeight((num_labels, self.out_channels), False, SN_EPS_CONV)
-        with torch.no_grad():
-            self.embed.weight_orig.uniform_(-0.1, 0.1)
-        self.finetuning = False
+
+    def _stem(self):
+        k0, k2 = self.STEM_KEYS
+        return self.down_block._modules[k0], self.down_block._modules[k2], self.skip._modules['0']
 
     def _fresh_packs(self):
         """16-bit packs (forward + dgrad) of every conv of the critic for this step's three passes, one batched launch per operand mode in
         use (the default mode; the fake -> G pass's strict mode for the layers it covers: ``gpass_prec``) -> {mode: {(W_orig.data_ptr(),
         orientation): pack}}, the inner dicts keyed like ConvFn's per-step cache"""
-        d0, d2, sk = self.down_block._modules['0'], self.down_block._modules['2'], self.skip._modules['0']
+        d0, d2, sk = self._stem()
         units = [[d0, d2, sk]] + [blk.sn_layers() for blk in self.blocks]          # unit 0 = stem, 1.. = blocks (gpass_prec's numbering)
         if not d0.weight_orig.is_cuda:
             return {}
         training = self.training and torch.is_grad_enabled()
         out = {}
         strict_from = {}          # operand mode other than the default one -> first unit any pass runs in it
-        for sprec, sfrom in (gpass_prec(), dpass_prec()):
-            if sprec != default_prec() and training:
+        for sprec, sfrom in self._strict_modes():
+            if sprec != self._base_prec() and training:
                 strict_from[sprec] = min(sfrom, strict_from.get(sprec, sfrom))
-        for prec, convs in [(default_prec(), [m for u in units for m in u])] + [(sp, [m for u in units[sf:] for m in u]) for sp, sf in strict_from.items()]:
+        for prec, convs in [(self._base_prec(), [m for u in units for m in u])] + [(sp, [m for u in units[sf:] for m in u]) for sp, sf in strict_from.items()]:
             if not convs:
                 continue
             # conv + pool launches (nn.ConvPoolFn: the stem's second conv, conv2 of every down block) take the 16-tap images of modes 4 / 5
@@ -233,11 +234,97 @@ class Discriminator(nn.Module):
     def _conv_sn_layers(self):
         layers = self.__dict__.get('_sn_layer_cache')
         if layers is None:
-            d0, d2, sk = self.down_block._modules['0'], self.down_block._modules['2'], self.skip._modules['0']
-            layers = [d0, d2, sk] + [l for blk in self.blocks for l in blk.sn_layers()] + [self.linear]
+            d0, d2, sk = self._stem()
+            layers = [d0, d2, sk] + [l for blk in self.blocks for l in blk.sn_layers()] + self._head_layers()
             self.__dict__['_sn_layer_cache'] = layers
             self.__dict__['_sn_batch'] = SNBatch(layers)
         return layers
+
+    def _stem_source(self, x, pooled=False):
+        """what the stem's first convs read: the NHWC image (``pooled``: its AvgPool2d(2), for the 1x1 skip conv that commutes with the pool)"""
+        return to_nhwc(F.avg_pool2d(x, 2) if pooled else x)
+
+    def _stem_conv(self, xn, layer, track, states, prec, **kw):
+        return _conv(xn, layer, track, states, prec, **kw)
+
+    def _trunk(self, x, track_weights, states, strict=None):
+        """stem + blocks on the logical N x C x H x W image ``x`` -> (pre-activation output of the last block, NHWC; feature list)"""
+        d0, d2, sk = self._stem()
+        xn = self._stem_source(x)
+        sprec, sfrom = strict if strict is not None else (None, 0)
+        unit_prec = lambda u: sprec if (sprec is not None and u >= sfrom) else None          # None = the default mode
+        p0 = unit_prec(0)
+        h, h16 = self._stem_conv(xn, d0, track_weights, states, p0, ksize=3, emit16=1, want_y=not PLANES_ONLY)
+        nb = len(self.blocks)
+        if CONV_POOL:
+            # stem: pool(conv2(relu(h)) + skip(image)) as one launch; the skip conv (3 -> 64, 1x1) runs on the pooled image
+            shortcut_lo = self._stem_conv(self._stem_source(x, pooled=True), sk, track_weights, states, p0, ksize=1)
+            pp0 = default_prec() if p0 is None else p0
+            np1 = unit_prec(1) if nb else None
+            holder = [] if (default_prec() if np1 is None else np1) == pp0 else None
+            out_relu = _conv_pool(h, d2, track_weights, states, p0, shortcut_lo, h16, True, holder)
+            xr16 = holder[0] if holder else None
+        else:
+            shortcut = self._stem_conv(xn, sk, track_weights, states, p0, ksize=1)
+            out_relu, xr16 = pool_relu(_conv(h, d2, track_weights, states, p0, res=shortcut, ksize=3, pro=2, x16=h16), unit_prec(1) if nb else None)
+        feats = []
+        out = out_relu
+        for bi, block in enumerate(self.blocks):
+            # out_relu = relu(previous unit's output): what the reference's in-place ReLU leaves behind in its feature list
+            lpnn.tape_relu(lambda: out_relu > 0)
+            feats.append(as_nchw_view(out_relu))
+            last = bi + 1 == nb
+            res = block(out_relu, track_weights, states, unit_prec(bi + 1), xr16=xr16, next_prec=None if last else unit_prec(bi + 2), last=last)
+            if block.downsample and not last:
+                out_relu, xr16 = res
+                out = out_relu
+            else:
+                out = res
+                if bi + 1 < nb:          # (a non-pooling block in the middle of the stack: its successor's in-place ReLU)
+                    out_relu, xr16 = torch.relu(out), None
+        feats.append(as_nchw_view(out))
+        lpnn.tape_relu(lambda: out > 0)
+        return out, feats
+
+
+class Discriminator(ResTrunk):
+    # positions of the stem's two convs inside ``down_block`` (the state-dict keys): no_landmarks.py:52-60 has its `padding(1)` entries commented
+    # out; the FSTH family (discriminators/FSTH.py, embedders/FSTH.py) keeps them -> ('1', '4')
+    STEM_KEYS = ('0', '2')
+
+    def __init__(self, padding, in_channels, out_channels, num_channels, max_num_channels, embed_channels, dis_num_blocks,
+                 image_size, num_labels):
+        super().__init__()
+        if padding not in ('zero', 'reflection'):
+            raise Exception('Incorrect `padding` argument, required `zero` or `reflection`')       # (no_landmarks.py:49-50)
+        reflect = padding == 'reflection'          # (the stem's convs keep their zero padding: no_landmarks.py:52-60 has `padding(1)` commented out)
+        self.out_channels = embed_channels
+        self._build_stem(in_channels, num_channels)
+        self.blocks = nn.ModuleList()
+        num_down = min(int(math.log(image_size, 2)) - 2, dis_num_blocks)
+        cin = num_channels
+        cout = cin
+        for i in range(1, num_down):
+            cout = min(cin * 2, max_num_channels)
+            if i == dis_num_blocks - 1:
+                cout = self.out_channels
+            self.blocks.append(_DisBlock(cin, cout, True, reflect))
+            cin = cout
+        for i in range(num_down, dis_num_blocks):
+            if i == dis_num_blocks - 1:
+                cout = self.out_channels
+            self.blocks.append(_DisBlock(cin, cout, False, reflect))
+        self.linear = SNWeight((1, self.out_channels), True, SN_EPS_CONV)
+        self.embed = SNWeight((num_labels, self.out_channels), False, SN_EPS_CONV)
+        with torch.no_grad():
+            self.embed.weight_orig.uniform_(-0.1, 0.1)
+        self.finetuning = False
+
+    def _strict_modes(self):
+        return (gpass_prec(), dpass_prec())
+
+    def _head_layers(self):
+        return [self.linear]
 
     def _embed_batch(self):
         esn = self.__dict__.get('_embed_sn')
@@ -262,7 +349,6 @@ class Discriminator(nn.Module):
         (1..) from that unit on run in that operand mode instead of the default one (the fake -> G pass)."""
         if not x.is_cuda:
             raise RuntimeError('the discriminator runs on the MI355X HIP path only (no CPU fallback)')
-        d0, d2, sk = self.down_block._modules['0'], self.down_block._modules['2'], self.skip._modules['0']
         # one launch power-iterates all spectrally normalised layers of this pass (every pass does its own iteration; prepare_step() may
         # have run the three iterations of this step ahead)
         layers = self._conv_sn_layers()
@@ -270,40 +356,7 @@ class Discriminator(nn.Module):
         st = sn_states if sn_states is not None else (ahead.pop(0) if ahead else self._sn_batch.update(self.training))
         states = {id(l): s for l, s in zip(layers, st)}
         states['packs'] = self.__dict__.setdefault('_step_packs', {})
-        xn = to_nhwc(x)
-        sprec, sfrom = strict if strict is not None else (None, 0)
-        unit_prec = lambda u: sprec if (sprec is not None and u >= sfrom) else None          # None = the default mode
-        p0 = unit_prec(0)
-        h, h16 = _conv(xn, d0, track_weights, states, p0, ksize=3, emit16=1, want_y=not PLANES_ONLY)
-        nb = len(self.blocks)
-        if CONV_POOL:
-            # stem: pool(conv2(relu(h)) + skip(image)) as one launch; the skip conv (3 -> 64, 1x1) runs on the pooled image
-            shortcut_lo = _conv(to_nhwc(F.avg_pool2d(x, 2)), sk, track_weights, states, p0, ksize=1)
-            pp0 = default_prec() if p0 is None else p0
-            np1 = unit_prec(1) if nb else None
-            holder = [] if (default_prec() if np1 is None else np1) == pp0 else None
-            out_relu = _conv_pool(h, d2, track_weights, states, p0, shortcut_lo, h16, True, holder)
-            xr16 = holder[0] if holder else None
-        else:
-            shortcut = _conv(xn, sk, track_weights, states, p0, ksize=1)
-            out_relu, xr16 = pool_relu(_conv(h, d2, track_weights, states, p0, res=shortcut, ksize=3, pro=2, x16=h16), unit_prec(1) if nb else None)
-        feats = []
-        out = out_relu
-        for bi, block in enumerate(self.blocks):
-            # out_relu = relu(previous unit's output): what the reference's in-place ReLU leaves behind in its feature list
-            lpnn.tape_relu(lambda: out_relu > 0)
-            feats.append(as_nchw_view(out_relu))
-            last = bi + 1 == nb
-            res = block(out_relu, track_weights, states, unit_prec(bi + 1), xr16=xr16, next_prec=None if last else unit_prec(bi + 2), last=last)
-            if block.downsample and not last:
-                out_relu, xr16 = res
-                out = out_relu
-            else:
-                out = res
-                if bi + 1 < nb:          # (a non-pooling block in the middle of the stack: its successor's in-place ReLU)
-                    out_relu, xr16 = torch.relu(out), None
-        feats.append(as_nchw_view(out))
-        lpnn.tape_relu(lambda: out > 0)
+        out, feats = self._trunk(x, track_weights, states, strict)
         pooled, dot = lpnn.ProjScoreFn.apply(out, embed)          # sum_hw relu(out) and <pooled, embed> in one launch
         wl, bl, sl = _wb(self.linear, track_weights, states)
         score = SNLinearFn.apply(pooled, wl, bl, *sl)[:, 0]

@@ -1,0 +1,147 @@
+"""Shared host code of the FSTH plugin family (embedders/FSTH.py, embedders/no_pose_encoder.py, discriminators/FSTH.py of the reference): nets whose
+first layer sees a rendered stickman next to the image.  They are the critic's stem + norm-'none' down blocks (discriminators/no_landmarks.ResTrunk);
+the stickman and the image stay two tensors up to the first convs, which read them through a channel map (nn.StemInput -> csrc/conv_stem8.hip)."""
+import os
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from latent_pose_reenactment_amd import hipops as ops
+from latent_pose_reenactment_amd import nn as lpnn
+from latent_pose_reenactment_amd.discriminators import no_landmarks as _critic
+from latent_pose_reenactment_amd.nn import EmbedTailFn, StemInput, default_prec
+
+
+def concat_order(cs, cr):
+    """torch.cat([stickmen, rgbs], 2) of 5-D B x K x C x H x W tensors (embedders/FSTH.py:74): (s0 .. s_cs-1, r0 .. r_cr-1)"""
+    return [(0, c) for c in range(cs)] + [(1, c) for c in range(cr)]
+
+
+def interleaved_order(cs, cr):
+    """torch.cat([stickmen, rgbs], dim=2).view(b, -1, h, w) of 4-D B x C x H x W tensors (discriminators/FSTH.py:153-158): the concatenation runs
+    over the image ROWS and the view cuts every 2h-row plane into two channels -> (s0, r0, s1, r1, ...); needs as many stickman as image channels"""
+    if cs != cr:
+        raise ValueError(f'the FSTH discriminator concatenates stickman and image along dim 2: their channel counts must agree ({cs} vs {cr})')
+    return [(j % 2, j // 2) for j in range(2 * cs)]
+
+
+class TwoSourceStem:
+    """mixin of a ``ResTrunk`` whose stem reads (stickman, image): ``_set_stick`` names the stickman of the coming passes; ``_trunk`` is then called
+    with the image alone, as in the RGB critic.  Without a stickman set the stem is the plain one."""
+    STEM_KEYS = ('1', '4')          # the FSTH family keeps `padding(1)` in front of both stem convs: down_block.1 / down_block.4
+    CHANNEL_ORDER = staticmethod(concat_order)
+
+    def _set_stick(self, stick):
+        """``stick``: N x Cs x H x W, a constant for autograd; its AvgPool2d(2) (input of the 1x1 skip conv, which commutes with the pool) is taken
+        here, once for all passes and on the caller's stream"""
+        if stick is None:
+            self.__dict__['_stick'] = None
+            return
+        stick = stick.detach()
+        self.__dict__['_stick'] = (stick, F.avg_pool2d(stick, 2) if _critic.CONV_POOL else None)
+
+    def _stem_source(self, x, pooled=False):
+        st = self.__dict__.get('_stick')
+        if st is None:
+            return super()._stem_source(x, pooled)
+        stick, stick_lo = st
+        if stick.shape[0] != x.shape[0] or stick.shape[2:] != x.shape[2:]:
+            raise ValueError(f'stickman {tuple(stick.shape)} and image {tuple(x.shape)} differ in batch or size')
+        cs, cr = stick.shape[1], x.shape[1]
+        cmap = ops.stem8_cmap(self.CHANNEL_ORDER(cs, cr))
+        if pooled:
+            return StemInput(stick_lo, F.avg_pool2d(x, 2), cmap, cs + cr)
+        return StemInput(stick, x, cmap, cs + cr)
+
+    def _stem_conv(self, xn, layer, track, states, prec, **kw):
+        if not isinstance(xn, StemInput):
+            return super()._stem_conv(xn, layer, track, states, prec, **kw)
+        w, b, st = _critic._wb(layer, track, states)
+        prec = default_prec() if prec is None else prec
+        return lpnn.hip_stem_conv(xn, w, b, ksize=kw['ksize'], prec=prec, packs=states['packs'].setdefault(prec, {}), sn=st,
+                                  emit16=kw.get('emit16'), want_y=kw.get('want_y', True))
+
+
+def refuse_reflection(padding, flag):
+    """the reference's FSTH family reflect-pads its STEM convs too (unlike no_landmarks, where the stem's padding is commented out); the stem's
+    conv + pool launch is zero-padded only, so the flag is refused instead of being run with the wrong border"""
+    if padding not in ('zero', 'reflection'):
+        raise Exception('Incorrect `padding` argument, required `zero` or `reflection`')
+    if padding == 'reflection':
+        raise NotImplementedError(f'{flag} reflection is not implemented for the FSTH plugin family (its stem convs would be reflection-padded too); '
+                                  f'use {flag} zero')
+
+
+def embedder_prec():
+    """operand mode of the conv embedders: ``LP_PREC_E_FSTH`` if set, else bf16x3 under the global fp16 mode (13 convs behind each other and gradients
+    gated at 1e-3 per parameter: the assignment the generator's 17-layer decoder needed; fp16 is the opt-in), the global mode otherwise"""
+    name = os.environ.get('LP_PREC_E_FSTH')
+    if name:
+        return lpnn.PREC_NAMES[name]
+    return lpnn.PREC_BF16X3 if default_prec() == lpnn.PREC_F16 else default_prec()
+
+
+class ConvEmbedder(TwoSourceStem, _critic.ResTrunk):
+    """identity encoder of embedders/FSTH.py (``with_stickman``: 6-channel stem on enc_stickmen (+) enc_rgbs) and embedders/no_pose_encoder.py
+    (3-channel stem on enc_rgbs): stem, ``embed_num_blocks - 1`` down blocks, ReLU, sum over H x W, mean | max over the K frames"""
+
+    def __init__(self, padding, in_channels, out_channels, num_channels, max_num_channels, embed_channels, embed_num_blocks, average_function,
+                 with_stickman):
+        super().__init__()
+        refuse_reflection(padding, '--embed_padding')
+        if average_function not in ('sum', 'max'):
+            raise Exception('Incorrect `average_function` argument, expected `sum` or `max`')
+        self.out_channels = embed_channels
+        self.with_stickman = with_stickman
+        self._build_stem(in_channels + out_channels if with_stickman else 3, num_channels)
+        layers = []
+        cin, cout = num_channels, out_channels          # (FSTH.py:56-62: the last block's input width is whatever the loop left in `out_channels`)
+        for _ in range(1, embed_num_blocks - 1):
+            cout = min(cin * 2, max_num_channels)
+            layers.append(_critic._DisBlock(cin, cout, True))
+            cin = cout
+        layers.append(_critic._DisBlock(cout, embed_channels, True))
+        self.down_blocks = nn.ModuleList(layers)
+        self.average_function = average_function
+        self.finetuning = False
+
+    @property
+    def blocks(self):
+        return self.down_blocks
+
+    def _base_prec(self):
+        return embedder_prec()
+
+    def enable_finetuning(self, data_dict=None):
+        self.finetuning = True
+
+    def get_identity_embedding(self, data_dict):
+        rgbs = data_dict['enc_rgbs']
+        if not rgbs.is_cuda:
+            raise RuntimeError('the embedder runs on the MI355X HIP path only (no CPU fallback)')
+        b, k, c, h, w = rgbs.shape
+        x = rgbs.reshape(b * k, c, h, w)
+        if self.with_stickman:
+            stick = data_dict['enc_stickmen']
+            self._set_stick(stick.reshape(b * k, stick.shape[2], h, w))
+        self.__dict__['_step_packs'] = self._fresh_packs()          # new step: the optimizer has changed W_orig
+        layers = self._conv_sn_layers()
+        states = {id(l): s for l, s in zip(layers, self._sn_batch.update(self.training))}
+        states['packs'] = self.__dict__['_step_packs']
+        prec = embedder_prec()
+        try:
+            out, _ = self._trunk(x, True, states, (prec, 0) if prec != default_prec() else None)
+        finally:
+            self._set_stick(None)
+        embeds, elemwise = EmbedTailFn.apply(out, b, k, self.average_function == 'max')
+        data_dict['embeds'] = embeds
+        data_dict['embeds_elemwise'] = elemwise
+
+    def get_pose_embedding(self, data_dict):
+        pass
+
+    def forward(self, data_dict):
+        if not self.finetuning:
+            self.get_identity_embedding(data_dict)
+        self.get_pose_embedding(data_dict)

@@ -376,6 +376,132 @@ def thin_conv(x: Tensor, pack: WeightPack, *, ksize: int, bias: Optional[Tensor]
     return y, act_pack(y, pro=2 if out16 else 0, prec=oprec)
 
 
+# ---- first layer of the stickman-conditioned nets: 5..8 input channels gathered from TWO fp32 tensors (csrc/conv_stem8.hip) -------------------
+def stem8_cmap(order) -> int:
+    """channel map of a two-source conv input: ``order`` = [(source 0 | 1, channel inside that source)] per conv input channel -> packed nibbles"""
+    order = list(order)
+    assert 5 <= len(order) <= 8 and all(s in (0, 1) and 0 <= c < 8 for s, c in order), order
+    v = 0
+    for i, (s, c) in enumerate(order):
+        v |= ((s << 3) | c) << (4 * i)
+    return v
+
+
+def stem8_cmap_order(cmap: int, cin: int):
+    return [((cmap >> (4 * i + 3)) & 1, (cmap >> (4 * i)) & 7) for i in range(cin)]
+
+
+# The two-source route has not been timed against the generic one on an MI355X yet (scripts/stem8_micro.py), so it is OPT-IN: LP_STEM8=1 routes the
+# first convs of the FSTH family through csrc/conv_stem8.hip; the default is the generic MFMA path on the materialised concatenation.
+_STEM8 = os.environ.get('LP_STEM8', '0') != '0'
+
+
+def stem8_supported(cin: int, cout: int, ksize: int, w: int) -> bool:
+    """the two-source kernels cover the shape (LP_THIN=0: never -- the test knob sends every thin-channel layer through the generic MFMA path)"""
+    return _THIN and bool(_lib.lib().lp_stem8_supported(cin, cout, ksize, w))
+
+
+def stem8_route(cin: int, cout: int, ksize: int, w: int) -> bool:
+    """the first layer of a two-source input runs on the two-source kernels: LP_STEM8=1 and a covered shape"""
+    return _STEM8 and stem8_supported(cin, cout, ksize, w)
+
+
+def _src4(t: Optional[Tensor], name: str):
+    """logical N x C x H x W fp32 CUDA tensor with ANY strides -> (pointer, 4 element strides as a C array, channels)"""
+    import ctypes
+    if t is None:
+        return None, None, 0
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise ValueError(f'{name}: expected a 4-D fp32 CUDA tensor, got {t.dtype} {t.device} dim={t.dim()}')
+    return t.data_ptr(), (ctypes.c_longlong * 4)(*t.stride()), t.shape[1]
+
+
+def _c_int32(v: int) -> int:
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+def stem8_conv(xa: Optional[Tensor], xb: Optional[Tensor], cmap: int, pack: WeightPack, *, ksize: int, cin: int, bias: Optional[Tensor] = None,
+               alpha: Optional[Tensor] = None, prec: int = PREC_BF16, out16: Optional[int] = None, want_y: bool = True):
+    """y [N,H,W,Cout] = alpha * conv(concat_by_cmap(xa, xb), pack) + bias on the matrix cores, the sources read in place (logical NCHW, any strides).
+    ``out16`` = 0 | 1: also return the operand planes of y (1: of relu(y)), written by the same launch -> (y, Act16); ``want_y=False``: planes only."""
+    import ctypes
+    ref = xa if xa is not None else xb
+    n, _, h, w = ref.shape
+    assert xa is None or xb is None or (xa.shape[0], xa.shape[2], xa.shape[3]) == (xb.shape[0], xb.shape[2], xb.shape[3]), (xa.shape, xb.shape)
+    cout = pack.rows
+    assert want_y or out16 is not None
+    y = torch.empty((n, h, w, cout), dtype=torch.float32, device=ref.device) if want_y else None
+    o_hi, o_lo = _alloc16(n, h, w, cout, prec, ref.device) if out16 is not None else (None, None)
+    pa, sa, ca = _src4(xa, 'xa')
+    pb, sb, cb = _src4(xb, 'xb')
+    pl = 4 if prec == PREC_BF16X3 else 2
+    nbytes = (n * h * w * cin * 4, n * h * w * cout * ((4 if want_y else 0) + (pl if out16 is not None else 0)))
+    with _Timed('conv_thin', 2.0 * n * h * w * cout * cin * ksize * ksize, (n, h, w, cin, cout, ksize, 0, 0), nbytes, mm=3 if prec == PREC_BF16X3 else 1):
+        check(_lib.lib().lp_stem8_fwd(pa, None if sa is None else ctypes.addressof(sa), ca, pb, None if sb is None else ctypes.addressof(sb), cb,
+                                      _c_int32(cmap), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(alpha), n, h, w, cin, cout, pack.cols_p,
+                                      pack.rows_p, ksize, prec, _p(o_hi), _p(o_lo), int(bool(out16)), _stream()), 'lp_stem8_fwd')
+    if out16 is None:
+        return y
+    return y, Act16(o_hi, o_lo, cout, None)
+
+
+def stem8_wgrad(xa: Optional[Tensor], xb: Optional[Tensor], cmap: int, dy: Tensor, *, ksize: int, cin: int, sn=None, accum: Optional[Tensor] = None,
+                bias_grad: bool = False):
+    """dw [Cout,Cin,k,k] (and db [Cout]) of ``stem8_conv`` from the fp32 gradient dy [N,H,W,Cout]; fp32, the same summation order in every run.
+    ``sn`` / ``accum`` as in ``conv_wgrad16``."""
+    import ctypes
+    _chk(dy, 'dy')
+    n, h, w, cout = dy.shape
+    ws = torch.empty(_lib.lib().lp_stem8_wgrad_workspace_bytes(n, h, cout, ksize) // 4, dtype=torch.float32, device=dy.device)
+    dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=dy.device)
+    db = torch.empty(cout, dtype=torch.float32, device=dy.device) if bias_grad else None
+    pa, sa, ca = _src4(xa, 'xa')
+    pb, sb, cb = _src4(xb, 'xb')
+    with _Timed('wgrad_thin', 2.0 * n * h * w * cout * cin * ksize * ksize, (n, h, w, cin, cout, ksize, 0, 0), (n * h * w * (cout + cin) * 4, dw.numel() * 4)):
+        check(_lib.lib().lp_stem8_wgrad(pa, None if sa is None else ctypes.addressof(sa), ca, pb, None if sb is None else ctypes.addressof(sb), cb,
+                                        _c_int32(cmap), dy.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), n, h, w, cin, cout, ksize, _stream()),
+              'lp_stem8_wgrad')
+    dw = _sn_finish(dw, sn, accum)
+    return (dw, db) if bias_grad else dw
+
+
+def stem8_dgrad(dy: Tensor, w_orig: Tensor, alpha: Optional[Tensor], cmap: int, cb: int, *, ksize: int) -> Tensor:
+    """gradient of ``stem8_conv`` w.r.t. its SECOND source (the image; the stickman has none) -> contiguous N x Cb x H x W; fp32 on fp32 W_orig"""
+    import ctypes
+    _chk(dy, 'dy'); _chk(w_orig, 'w_orig')
+    n, h, w, cout = dy.shape
+    cin = w_orig.shape[1]
+    dx = torch.empty((n, cb, h, w), dtype=torch.float32, device=dy.device)
+    st = (ctypes.c_longlong * 4)(*dx.stride())
+    with _Timed('conv_thin', 2.0 * n * h * w * cout * cb * ksize * ksize, (n, h, w, cout, cb, ksize, 0, 0), (dy.numel() * 4, dx.numel() * 4)):
+        check(_lib.lib().lp_stem8_dgrad(dy.data_ptr(), w_orig.data_ptr(), _p(alpha), dx.data_ptr(), ctypes.addressof(st), cb, _c_int32(cmap), n, h, w,
+                                        cin, cout, ksize, _stream()), 'lp_stem8_dgrad')
+    return dx
+
+
+def embed_tail_fwd(out: Tensor, b: int, k: int, use_max: bool):
+    """conv embedders' tail: out [B*K,H,W,C] -> (embeds_elemwise [B,K,C] = sum_hw relu(out), embeds [B,C] = mean | max over K, argk | None), one launch"""
+    _chk(out, 'out')
+    bk, h, w, c = out.shape
+    assert bk == b * k, (out.shape, b, k)
+    elem = torch.empty((b, k, c), dtype=torch.float32, device=out.device)
+    embeds = torch.empty((b, c), dtype=torch.float32, device=out.device)
+    argk = torch.empty((b, c), dtype=torch.int32, device=out.device) if use_max else None
+    check(_lib.lib().lp_embed_tail_fwd(out.data_ptr(), elem.data_ptr(), embeds.data_ptr(), _p(argk), b, k, h * w, c, int(use_max), _stream()), 'lp_embed_tail_fwd')
+    return elem, embeds, argk
+
+
+def embed_tail_bwd(out: Tensor, g_elem: Optional[Tensor], g_embeds: Optional[Tensor], argk: Optional[Tensor], b: int, k: int, use_max: bool) -> Tensor:
+    for t, nm in ((g_elem, 'g_elem'), (g_embeds, 'g_embeds')):
+        if t is not None:
+            _chk(t, nm)
+    bk, h, w, c = out.shape
+    d_out = torch.empty_like(out)
+    check(_lib.lib().lp_embed_tail_bwd(out.data_ptr(), _p(g_elem), _p(g_embeds), _p(argk), d_out.data_ptr(), b, k, h * w, c, int(use_max), _stream()),
+          'lp_embed_tail_bwd')
+    return d_out
+
+
 def conv(x: Tensor, pack: WeightPack, *, ksize: int, upsample: bool = False, pro: int = 0, scale: Optional[Tensor] = None,
          shift: Optional[Tensor] = None, bias: Optional[Tensor] = None, res: Optional[Tensor] = None, res_shift: int = 0,
          alpha: Optional[Tensor] = None, prec: int = PREC_BF16, relu_mask: Optional[Tensor] = None, grad: bool = False) -> Tensor:

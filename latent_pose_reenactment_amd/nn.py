@@ -12,7 +12,7 @@ from __future__ import annotations
 import math
 import os
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -1177,6 +1177,110 @@ def hip_conv(x, w, bias=None, res=None, ksize=3, pro=0, prec=None, packs=None, s
     holder = []
     y = ConvFn.apply(x, w, bias, res, ksize, pro, prec, packs, sn, x16, (int(emit16), holder) + ((() if emit_prec is None else (emit_prec,)) if want_y else (emit_prec, False)))
     return y, holder[0]
+
+
+class StemInput(NamedTuple):
+    """input of a stickman-conditioned first layer: the channel concatenation (by ``cmap``, hipops.stem8_cmap) of two logical N x C x H x W tensors,
+    ``xa`` (the stickman: a constant for autograd) and ``xb`` (the image); never materialised where the two-source kernels run"""
+    xa: torch.Tensor
+    xb: torch.Tensor
+    cmap: int
+    cin: int
+
+    def dense(self) -> torch.Tensor:
+        """the concatenated tensor itself, N x Cin x H x W (generic path; autograd reaches ``xb`` through it)"""
+        srcs = (self.xa, self.xb)
+        return torch.cat([srcs[s][:, c:c + 1] for s, c in ops.stem8_cmap_order(self.cmap, self.cin)], dim=1)
+
+
+class Stem8Fn(torch.autograd.Function):
+    """y = conv_{k x k, zero pad}(concat_by_cmap(xa, xb), w) + bias for 5..8 input channels (csrc/conv_stem8.hip): forward on the matrix cores straight
+    from the two sources, optionally emitting the operand planes of relu(y) (``emit`` as in ConvFn); backward = fp32 weight / bias gradient
+    (lp_stem8_wgrad) and the data gradient w.r.t. ``xb`` only (lp_stem8_dgrad)."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, w, bias, ksize, cmap, prec, packs, sn, emit):
+        wd = w.detach().contiguous()
+        cout, cin = wd.shape[0], wd.shape[1]
+        small_k = ksize == 3 and cin <= 32
+        want_y = not (emit is not None and len(emit) > 3 and emit[3] is False)
+        assert emit is None or len(emit) < 3 or emit[2] in (None, prec), 'the planes are emitted in the conv\'s own operand mode'
+        if isinstance(packs, dict):
+            key = (wd.data_ptr(), 0)
+            if key not in packs:
+                packs[key] = ops.pack_weights(wd, 0, prec, small_k=small_k)
+            pack = packs[key]
+        else:
+            pack = packs[0] if packs is not None else ops.pack_weights(wd, 0, prec, small_k=small_k)
+        bd = None if bias is None else bias.detach().contiguous()
+        alpha = None if sn is None else sn[2][1:]
+        xa, xb = xa.detach(), xb.detach()
+        y = ops.stem8_conv(xa, xb, cmap, pack, ksize=ksize, cin=cin, bias=bd, alpha=alpha, prec=prec, out16=None if emit is None else emit[0],
+                           want_y=want_y)
+        if emit is not None:
+            y, o16 = y
+            emit[1].append(o16)
+            if emit[0]:
+                tape_relu(lambda: o16.hi[..., :cout] > 0, True)
+        if y is None:
+            y = phantom((xb.shape[0], xb.shape[2], xb.shape[3], cout), xb.device)
+        ctx.xa, ctx.xb, ctx.wd = xa, xb, wd
+        ctx.w_param = w if (sn is not None and w.requires_grad and w.is_leaf) else None
+        ctx.accum_alt = _ALT['on']
+        ctx.cfg = (ksize, cmap, bias is not None, sn)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ksize, cmap, has_bias, sn = ctx.cfg
+        wd = ctx.wd
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dx = ops.stem8_dgrad(dy, wd, None if sn is None else sn[2][1:], cmap, ctx.xb.shape[1], ksize=ksize)
+        want_db = has_bias and ctx.needs_input_grad[3]
+        if ctx.needs_input_grad[2]:
+            dw = ops.stem8_wgrad(ctx.xa, ctx.xb, cmap, dy, ksize=ksize, cin=wd.shape[1], sn=None if sn is None else (wd,) + tuple(sn),
+                                 accum=None if ctx.w_param is None else _accum_target(ctx.w_param, ctx.accum_alt), bias_grad=want_db)
+            if want_db:
+                dw, db = dw
+        elif want_db:
+            db = dy.sum(dim=(0, 1, 2))
+        return None, dx, dw, db, None, None, None, None, None, None
+
+
+def hip_stem_conv(x: StemInput, w, bias=None, ksize=3, prec=None, packs=None, sn=None, emit16=None, want_y=True):
+    """first layer on a two-source input: the two-source kernels where the route is on and covers the shape (hipops.stem8_route: LP_STEM8=1;
+    LP_THIN=0: never), else the generic ``hip_conv`` on the materialised concatenation.  ``emit16`` / ``want_y`` as in ``hip_conv``."""
+    prec = default_prec() if prec is None else prec
+    if not ops.stem8_route(x.cin, w.shape[0], ksize, x.xb.shape[3]):
+        return hip_conv(to_nhwc(x.dense()), w, bias, ksize=ksize, prec=prec, packs=packs, sn=sn, emit16=emit16, want_y=want_y)
+    _TAPE_GRAD[0] = torch.is_grad_enabled()
+    if emit16 is None:
+        return Stem8Fn.apply(x.xa, x.xb, w, bias, ksize, x.cmap, prec, packs, sn, None)
+    holder = []
+    y = Stem8Fn.apply(x.xa, x.xb, w, bias, ksize, x.cmap, prec, packs, sn, (int(emit16), holder) + (() if want_y else (None, False)))
+    return y, holder[0]
+
+
+class EmbedTailFn(torch.autograd.Function):
+    """tail of the conv embedders (embedders/FSTH.py:82-92 of the reference): out [B*K,H,W,C] -> (embeds [B,C], embeds_elemwise [B,K,C]) =
+    relu, sum over H x W, mean | max over the K frames -- one launch forward, one backward"""
+
+    @staticmethod
+    def forward(ctx, out, b, k, use_max):
+        o = out.detach().contiguous()
+        elem, embeds, argk = ops.embed_tail_fwd(o, b, k, use_max)
+        ctx.save_for_backward(o, argk)
+        ctx.cfg = (b, k, use_max)
+        return embeds, elem
+
+    @staticmethod
+    def backward(ctx, g_embeds, g_elem):
+        o, argk = ctx.saved_tensors
+        b, k, use_max = ctx.cfg
+        return ops.embed_tail_bwd(o, None if g_elem is None else g_elem.contiguous(), None if g_embeds is None else g_embeds.contiguous(), argk, b, k,
+                                  use_max), None, None, None
 
 
 class ConvPoolFn(torch.autograd.Function):
