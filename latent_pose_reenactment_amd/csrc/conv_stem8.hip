@@ -9,9 +9,10 @@
 //                planes of the input in LDS and 3 MFMAs per k-step.  The layer is bound by its output write (64 x 256^2 x 64 fp32 = 1.07 GB): the
 //                16 x 64 block goes through a wave-private LDS tile so that a pixel's channels leave as 256-byte runs, as fp32 y and / or as the
 //                operand planes of (relu?)(y) for the second stem conv (bit-identical to lp_act_pack of y).
-//   weight grad  fp32 on the VALU like the <= 4 channel kernel of conv_thin.hip (the work is a bandwidth-bound reduction over pixels: dy is streamed
-//                once, 64 channels per wave; the gathered input rows are broadcast from LDS, two 16-byte words per pixel).  Per-workgroup partial
-//                slabs + a fixed-order reduction: the same sum in every run.  The bias gradient comes from the same pass over dy.
+//   weight grad  fp32 on the VALU by the kernel the <= 4 channel convs of conv_thin.hip use (wgrad_rows_kernel of thin_rows.h: the work is a
+//                bandwidth-bound reduction over pixels: dy is streamed once, 64 channels per wave; the gathered input rows are broadcast from LDS,
+//                two 16-byte words per pixel).  Per-workgroup partial slabs + the fixed-order reduction of conv_thin.hip: the same sum in every
+//                run.  The bias gradient comes from the same pass over dy.
 //   data grad    to the IMAGE source only (the stickman has no gradient): 4 lanes share a pixel, each takes a quarter of the output channels of
 //                every tap from the fp32 dy rows (64 contiguous bytes per quad and load) against fp32 W_orig in LDS, then a 2-step quad reduction.
 #include "lp_common.h"
@@ -23,6 +24,7 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
+#include "thin_rows.h"      // (inside the region: the shared device code compiled into this file's kernels takes the attribute too)
 
 struct Stem8Src {
     const float* p;
@@ -129,48 +131,21 @@ __global__ __launch_bounds__(256) void conv_stem8_fwd_kernel(Stem8FwdParams p) {
                 for (int q = 0; q < 4; ++q) Tl[(kg * 4 + q) * 68 + nt * 16 + m] = acc[q];      // C: row = (lane>>4)*4 + q (pixel), col = lane&15
             }
             // (wave-private block: the LDS writes above are ordered before the reads below by the compiler's lgkmcnt wait)
-            const size_t pix = (size_t)(n * p.H + y0 + r) * p.W + x0 + pq;
-            float o[16];
-#pragma unroll
-            for (int j4 = 0; j4 < 4; ++j4) {
-                const float4 v = *(const float4*)(Tl + pq * 68 + cq + j4 * 4);
-                o[j4 * 4 + 0] = fmaf(v.x, alpha, bias16[j4 * 4 + 0]); o[j4 * 4 + 1] = fmaf(v.y, alpha, bias16[j4 * 4 + 1]);
-                o[j4 * 4 + 2] = fmaf(v.z, alpha, bias16[j4 * 4 + 2]); o[j4 * 4 + 3] = fmaf(v.w, alpha, bias16[j4 * 4 + 3]);
-                if (p.y) *(float4*)(p.y + pix * p.Cout + co0 + cq + j4 * 4) = make_float4(o[j4 * 4], o[j4 * 4 + 1], o[j4 * 4 + 2], o[j4 * 4 + 3]);
-            }
-            if (p.o_hi) {
-                s16x8_t h0, h1, l0, l1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float q0 = p.o_relu ? fmaxf(o[j], 0.f) : o[j], q1 = p.o_relu ? fmaxf(o[8 + j], 0.f) : o[8 + j];
-                    const uint16_t u0 = lp_f32_to_op16<F16>(q0), u1 = lp_f32_to_op16<F16>(q1);
-                    h0[j] = (short)u0; h1[j] = (short)u1;
-                    if (X3) {
-                        l0[j] = (short)lp_f32_to_op16<false>(q0 - lp_op16_to_f32<false>(u0));
-                        l1[j] = (short)lp_f32_to_op16<false>(q1 - lp_op16_to_f32<false>(u1));
-                    }
-                }
-                uint16_t* od = p.o_hi + pix * p.Cout + co0 + cq;
-                *(s16x8_t*)od = h0; *(s16x8_t*)(od + 8) = h1;
-                if (X3) {
-                    uint16_t* ol = p.o_lo + pix * p.Cout + co0 + cq;
-                    *(s16x8_t*)ol = l0; *(s16x8_t*)(ol + 8) = l1;
-                }
-            }
+            rows_store_tile<F16, X3>(Tl, pq, cq, alpha, bias16, (size_t)(n * p.H + y0 + r) * p.W + x0 + pq, p.y, p.o_hi, p.o_lo, p.Cout, co0, p.o_relu);
         }
     }
 }
 
 static size_t stem8_fwd_lds(int W, int ksize, int prec) {
-    const int pad = ksize / 2, rb = prec == LP_PREC_BF16X3 ? 2 : 4;
-    return (size_t)(rb + 2 * pad) * (W + 2 * pad) * 16 * (prec == LP_PREC_BF16X3 ? 2 : 1) + (size_t)4 * 16 * 68 * sizeof(float);
+    const bool x3 = prec == LP_PREC_BF16X3;      // hi + lo planes of the rows (16 bytes per pixel each), then the four waves' 16 x 68 fp32 tiles
+    return rows_lds_bytes(x3 ? 2 : 4, ksize / 2, W, x3 ? 32 : 16) + (size_t)4 * 16 * 68 * sizeof(float);
 }
 
 // one answer for the three operand modes and for forward + weight gradient (the callers route a layer as a whole): the widest staging decides
 static bool stem8_shape_ok(int Cin, int Cout, int ksize, int W) {
     if (Cin < 5 || Cin > 8 || Cout < 64 || (Cout % 64) != 0 || (ksize != 1 && ksize != 3) || W < 16 || (W % 16) != 0) return false;
     if (stem8_fwd_lds(W, ksize, LP_PREC_BF16X3) > 64 * 1024 || stem8_fwd_lds(W, ksize, LP_PREC_F16) > 64 * 1024) return false;
-    return (size_t)(4 + 2 * (ksize / 2)) * (W + 2 * (ksize / 2)) * 32 <= 64 * 1024;      // weight gradient: fp32 rows, 32 bytes per pixel
+    return RowsWgGeom<8>::lds_bytes(ksize, W) <= 64 * 1024;      // weight gradient: fp32 rows, 32 bytes per pixel
 }
 
 // the channel map must name, for every conv input channel, an existing channel of one of the two sources
@@ -206,152 +181,30 @@ extern "C" int lp_stem8_fwd(const float* xa, const long long* stride_a, int Ca, 
     p.a = stem8_src(xa, stride_a); p.b = stem8_src(xb, stride_b); p.cmap = (unsigned)cmap;
     p.w_hi = w_hi; p.w_lo = w_lo; p.y = y; p.bias = bias; p.alpha = alpha; p.o_hi = out_hi; p.o_lo = prec == LP_PREC_BF16X3 ? out_lo : nullptr;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.CinP = CinP; p.CoutP = CoutP; p.o_relu = out_relu;
-    const int rb = prec == LP_PREC_BF16X3 ? 2 : 4;
-    long long groups = (long long)N * ((H + rb - 1) / rb);
-    const int G = (int)(groups > 4096 ? 4096 : groups);
-    const size_t lds = stem8_fwd_lds(W, ksize, prec);
-    dim3 grid(G, Cout / 64);
-    hipStream_t s = (hipStream_t)stream;
-#define LP_STEM8_LAUNCH(MODE)                                                                                              \
-    if (ksize == 3) hipLaunchKernelGGL((conv_stem8_fwd_kernel<MODE, 3>), grid, dim3(256), lds, s, p);                     \
-    else hipLaunchKernelGGL((conv_stem8_fwd_kernel<MODE, 1>), grid, dim3(256), lds, s, p)
-    if (prec == LP_PREC_F16) { LP_STEM8_LAUNCH(LP_PREC_F16); }
-    else if (prec == LP_PREC_BF16X3) { LP_STEM8_LAUNCH(LP_PREC_BF16X3); }
-    else { LP_STEM8_LAUNCH(LP_PREC_BF16); }
-#undef LP_STEM8_LAUNCH
+    using Kernel = void (*)(Stem8FwdParams);
+    static const Kernel kernels[3][2] = {{conv_stem8_fwd_kernel<LP_PREC_BF16, 1>, conv_stem8_fwd_kernel<LP_PREC_BF16, 3>},      // [operand mode][3x3]
+                                         {conv_stem8_fwd_kernel<LP_PREC_BF16X3, 1>, conv_stem8_fwd_kernel<LP_PREC_BF16X3, 3>},
+                                         {conv_stem8_fwd_kernel<LP_PREC_F16, 1>, conv_stem8_fwd_kernel<LP_PREC_F16, 3>}};
+    static_assert(LP_PREC_BF16 == 0 && LP_PREC_BF16X3 == 1 && LP_PREC_F16 == 2, "the kernel table is indexed by the operand mode");
+    const dim3 grid(rows_groups(N, H, prec == LP_PREC_BF16X3 ? 2 : 4, 4096), Cout / 64);
+    hipLaunchKernelGGL(kernels[prec][ksize == 3], grid, dim3(256), stem8_fwd_lds(W, ksize, prec), (hipStream_t)stream, p);
     return lp_check_launch("conv_stem8_fwd");
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // Weight + bias gradient:  dw[co][ci][tap] = sum_{n,y,x} dy[n,y,x,co] * x[n, y+ky-1, x+kx-1, ci],  db[co] = sum dy[n,y,x,co]
 // ------------------------------------------------------------------------------------------------------------------
-struct Stem8WgParams {
+// source policy of wgrad_rows_kernel (thin_rows.h): the 5..8 channels of a pixel gathered from the two sources
+struct Stem8Gather {
     Stem8Src a, b; unsigned cmap;
-    const float* dy; float* part; float* bpart; float* dw; float* dbias;
-    int N, H, W, Cin, Cout, G;
+    __device__ __forceinline__ void load(const float*, int Cin, int n, int y, int x, int, int, float (&v)[8]) const {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (c < Cin) v[c] = stem8_load(a, b, cmap, c, n, y, x);
+    }
 };
 
-template <int KS>
-__global__ __launch_bounds__(256) void wgrad_stem8_kernel(Stem8WgParams p) {
-    constexpr int T = KS * KS, PAD = KS / 2, RB = 4, UB = (KS == 1) ? 16 : 8, TC = 4;      // TC: taps per round of the cross-wave reduction
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int tid = threadIdx.x, lane = tid & 63, ph = tid >> 6;
-    const int wc = blockIdx.y * 64 + lane;                               // this lane's output channel
-    const int RW = p.W + 2 * PAD;
-    float bsum = 0.f;
-    float acc[T][8];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) acc[t][c] = 0.f;
-    const int gpi = (p.H + RB - 1) / RB;
-    for (int grp = blockIdx.x; grp < p.N * gpi; grp += gridDim.x) {
-        const int n = grp / gpi, y0 = (grp % gpi) * RB;
-        __syncthreads();                                                 // previous group fully consumed
-        for (int i = tid; i < (RB + 2 * PAD) * RW; i += 256) {
-            const int r = i / RW, hx = i - r * RW;
-            const int iy = y0 + r - PAD, ix = hx - PAD;
-            float v[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = 0.f;
-            if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    if (c < p.Cin) v[c] = stem8_load(p.a, p.b, p.cmap, c, n, iy, ix);
-            }
-            *(float4*)(sm + (size_t)i * 8) = make_float4(v[0], v[1], v[2], v[3]);
-            *(float4*)(sm + (size_t)i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        }
-        __syncthreads();
-        const int nrow = min(RB, p.H - y0);
-        const int npx = nrow * p.W;                                      // pixels of the group, row-major; this wave: ph, ph+4, ...
-        const float* wbase = p.dy + (size_t)(n * p.H + y0) * p.W * p.Cout + wc;
-        for (int j0 = ph; j0 < npx; j0 += 4 * UB) {
-            float av[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int j = j0 + 4 * u;
-                av[u] = wbase[(size_t)(j < npx ? j : 0) * p.Cout];          // unconditional load, masked below
-            }
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int j = j0 + 4 * u;
-                const float a = j < npx ? av[u] : 0.f;
-                bsum += a;
-                const int rr = j / p.W, xx = j - rr * p.W;
-                const int jr = j < npx ? rr : 0;
-#pragma unroll
-                for (int ky = 0; ky < KS; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < KS; ++kx) {
-                        const float* q = sm + ((size_t)(jr + ky) * RW + xx + kx) * 8;
-                        const float4 v0 = *(const float4*)q, v1 = *(const float4*)(q + 4);
-                        float* ac = acc[ky * KS + kx];
-                        ac[0] = fmaf(a, v0.x, ac[0]); ac[1] = fmaf(a, v0.y, ac[1]); ac[2] = fmaf(a, v0.z, ac[2]); ac[3] = fmaf(a, v0.w, ac[3]);
-                        ac[4] = fmaf(a, v1.x, ac[4]); ac[5] = fmaf(a, v1.y, ac[5]); ac[6] = fmaf(a, v1.z, ac[6]); ac[7] = fmaf(a, v1.w, ac[7]);
-                    }
-            }
-        }
-    }
-    // sum the four pixel phases (waves) through LDS, TC taps per round, then one partial slab per workgroup: part[wg][tap][8][Cout]
-#pragma unroll
-    for (int t0 = 0; t0 < T; t0 += TC) {
-        __syncthreads();
-#pragma unroll
-        for (int tt = 0; tt < TC; ++tt)
-            if (t0 + tt < T) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) sm[((ph * TC + tt) * 8 + c) * 64 + lane] = acc[t0 + tt][c];
-            }
-        __syncthreads();
-        for (int i = tid; i < TC * 8 * 64; i += 256) {
-            const int l = i & 63, c = (i >> 6) & 7, tt = i >> 9;
-            if (t0 + tt < T) {
-                const float s = (sm[i] + sm[TC * 512 + i]) + (sm[2 * TC * 512 + i] + sm[3 * TC * 512 + i]);
-                p.part[(((size_t)blockIdx.x * T + t0 + tt) * 8 + c) * p.Cout + blockIdx.y * 64 + l] = s;
-            }
-        }
-    }
-    __syncthreads();
-    sm[tid] = bsum;
-    __syncthreads();
-    if (tid < 64) p.bpart[(size_t)blockIdx.x * p.Cout + blockIdx.y * 64 + tid] = (sm[tid] + sm[64 + tid]) + (sm[128 + tid] + sm[192 + tid]);
-}
-
-// dw[co][ci][tap] = sum_wg part[wg][tap][ci][co] in a fixed order (16 outputs x 16 slices of the G slabs per block, combined through LDS);
-// trailing blocks do the same for the bias partials
-__global__ __launch_bounds__(256) void wgrad_stem8_reduce_kernel(Stem8WgParams p, int T, int wblocks) {
-    __shared__ float red[16][17];
-    const bool is_bias = (int)blockIdx.x >= wblocks;
-    const int total = is_bias ? p.Cout : T * 8 * p.Cout;
-    const float* src = is_bias ? p.bpart : p.part;
-    const int o = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    const int idx = (is_bias ? (int)blockIdx.x - wblocks : (int)blockIdx.x) * 16 + o;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (idx < total) {
-        int g = sl;
-        for (; g + 48 < p.G; g += 64) {
-            a0 += src[(size_t)g * total + idx]; a1 += src[(size_t)(g + 16) * total + idx];
-            a2 += src[(size_t)(g + 32) * total + idx]; a3 += src[(size_t)(g + 48) * total + idx];
-        }
-        for (; g < p.G; g += 16) a0 += src[(size_t)g * total + idx];
-    }
-    red[sl][o] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (sl == 0 && idx < total) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s += red[k][o];
-        if (is_bias) { if (p.dbias) p.dbias[idx] = s; return; }
-        const int co = idx % p.Cout, c = (idx / p.Cout) & 7, t = idx / (p.Cout * 8);
-        if (c < p.Cin) p.dw[((size_t)co * p.Cin + c) * T + t] = s;
-    }
-}
-
-static int stem8_wgrad_groups(int N, int H) {
-    long long g = (long long)N * ((H + 3) / 4);
-    return (int)(g > 512 ? 512 : g);
-}
+static int stem8_wgrad_groups(int N, int H) { return rows_groups(N, H, RowsWgGeom<8>::RB, 512); }
 
 extern "C" long long lp_stem8_wgrad_workspace_bytes(int N, int H, int Cout, int ksize) {
     if (N < 1 || H < 1 || Cout < 1 || (ksize != 1 && ksize != 3)) return 0;
@@ -365,24 +218,19 @@ extern "C" int lp_stem8_wgrad(const float* xa, const long long* stride_a, int Ca
     if (N < 1 || H < 1) return lp_set_error(LP_ERR_ARG, "lp_stem8_wgrad: empty tensor");
     if (!stem8_shape_ok(Cin, Cout, ksize, W)) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_stem8_wgrad: needs 5 <= Cin <= 8, Cout % 64 == 0, 1x1 | 3x3, W % 16 == 0, rows that fit LDS");
     if (!stem8_cmap_ok((unsigned)cmap, Cin, Ca, Cb, xa != nullptr, xb != nullptr)) return lp_set_error(LP_ERR_ARG, "lp_stem8_wgrad: channel map names a channel outside its source");
-    Stem8WgParams p;
-    p.a = stem8_src(xa, stride_a); p.b = stem8_src(xb, stride_b); p.cmap = (unsigned)cmap;
-    p.dy = dy; p.dw = dw; p.dbias = dbias;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    Stem8Gather src;
+    src.a = stem8_src(xa, stride_a); src.b = stem8_src(xb, stride_b); src.cmap = (unsigned)cmap;
     const int T = ksize * ksize, G = stem8_wgrad_groups(N, H);
-    p.G = G;
+    RowsWgParams p;      // thin = the gathered input (8-channel slabs, zero padded), wide = dy; the bias partials follow the G slabs
+    p.x = nullptr; p.x16 = nullptr; p.scale = nullptr; p.shift = nullptr; p.pro = 0;
+    p.dy = dy; p.dw = dw; p.dbias = dbias;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.G = G;
     p.part = workspace; p.bpart = workspace + (size_t)G * T * 8 * Cout;
-    const size_t stage = (size_t)(4 + 2 * (ksize / 2)) * (W + 2 * (ksize / 2)) * 32, red = (size_t)4 * 4 * 8 * 64 * sizeof(float);
-    const size_t lds = stage > red ? stage : red;
-    dim3 grid(G, Cout / 64);
-    if (ksize == 3) hipLaunchKernelGGL(wgrad_stem8_kernel<3>, grid, dim3(256), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wgrad_stem8_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, p);
+    const auto kernel = ksize == 3 ? wgrad_rows_kernel<3, true, 8, true, Stem8Gather> : wgrad_rows_kernel<1, true, 8, true, Stem8Gather>;
+    hipLaunchKernelGGL(kernel, dim3(G, Cout / 64), dim3(256), RowsWgGeom<8>::lds_bytes(ksize, W), (hipStream_t)stream, p, src);
     int rc = lp_check_launch("wgrad_stem8");
     if (rc) return rc;
-    const int total = T * 8 * Cout;
-    const int wblocks = (total + 15) / 16, bblocks = (Cout + 15) / 16;
-    hipLaunchKernelGGL(wgrad_stem8_reduce_kernel, dim3(wblocks + bblocks), dim3(256), 0, (hipStream_t)stream, p, T, wblocks);
-    return lp_check_launch("wgrad_stem8_reduce");
+    return lp_wgrad_rows_reduce(p.part, p.bpart, dw, dbias, G, T, 8, Cin, Cout, true, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -5,10 +5,7 @@
 int lp_set_error(int code, const char* msg);
 int lp_check_launch(const char* what);
 
-// conv_thin.hip: fp32 VALU weight gradient for convs with <= 4 channels on one side
-bool lp_wgrad_thin_supported(int Cin, int Cout, int ksize, int upsample, int pro, int W);
-int lp_wgrad_thin(const float* x, const float* dy, float* dw, float* workspace, const float* scale, const float* shift, int N, int H,
-                  int W, int Cin, int Cout, int ksize, int pro, int splits, float* dbias, hipStream_t stream);
-bool lp_conv_thin_fwd_supported(int Cin, int Cout, int ksize, int upsample, int pro, bool has_res, int W);
-int lp_conv_thin_fwd(const float* x, const uint16_t* w_hi, const uint16_t* w_lo, float* y, const float* bias, const float* alpha, int N,
-                     int H, int W, int Cin, int Cout, int CinP, int CoutP, int ksize, int f16, hipStream_t stream);
+// conv_thin.hip: fixed-order reduction of the per-workgroup slabs of wgrad_rows_kernel (thin_rows.h), part[G][T][slabC][wideC] (thin channels
+// < thinC live) -> dw[Cout][Cin][T], and of the bias partials bpart[G][wideC] -> dbias (either NULL: none).  thin_x: the thin side is the input.
+int lp_wgrad_rows_reduce(const float* part, const float* bpart, float* dw, float* dbias, int G, int T, int slabC, int thinC, int wideC, bool thin_x,
+                         hipStream_t stream);

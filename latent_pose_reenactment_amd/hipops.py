@@ -407,13 +407,15 @@ def stem8_route(cin: int, cout: int, ksize: int, w: int) -> bool:
 
 
 def _src4(t: Optional[Tensor], name: str):
-    """logical N x C x H x W fp32 CUDA tensor with ANY strides -> (pointer, 4 element strides as a C array, channels)"""
+    """logical N x C x H x W fp32 CUDA tensor with ANY strides (or None) -> ((pointer, address of its 4 element strides, channels) as they go into
+    the C call, the stride array itself: the caller holds it until the call has returned)"""
     import ctypes
     if t is None:
-        return None, None, 0
+        return (None, None, 0), None
     if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
         raise ValueError(f'{name}: expected a 4-D fp32 CUDA tensor, got {t.dtype} {t.device} dim={t.dim()}')
-    return t.data_ptr(), (ctypes.c_longlong * 4)(*t.stride()), t.shape[1]
+    st = (ctypes.c_longlong * 4)(*t.stride())
+    return (t.data_ptr(), ctypes.addressof(st), t.shape[1]), st
 
 
 def _c_int32(v: int) -> int:
@@ -424,7 +426,6 @@ def stem8_conv(xa: Optional[Tensor], xb: Optional[Tensor], cmap: int, pack: Weig
                alpha: Optional[Tensor] = None, prec: int = PREC_BF16, out16: Optional[int] = None, want_y: bool = True):
     """y [N,H,W,Cout] = alpha * conv(concat_by_cmap(xa, xb), pack) + bias on the matrix cores, the sources read in place (logical NCHW, any strides).
     ``out16`` = 0 | 1: also return the operand planes of y (1: of relu(y)), written by the same launch -> (y, Act16); ``want_y=False``: planes only."""
-    import ctypes
     ref = xa if xa is not None else xb
     n, _, h, w = ref.shape
     assert xa is None or xb is None or (xa.shape[0], xa.shape[2], xa.shape[3]) == (xb.shape[0], xb.shape[2], xb.shape[3]), (xa.shape, xb.shape)
@@ -432,14 +433,12 @@ def stem8_conv(xa: Optional[Tensor], xb: Optional[Tensor], cmap: int, pack: Weig
     assert want_y or out16 is not None
     y = torch.empty((n, h, w, cout), dtype=torch.float32, device=ref.device) if want_y else None
     o_hi, o_lo = _alloc16(n, h, w, cout, prec, ref.device) if out16 is not None else (None, None)
-    pa, sa, ca = _src4(xa, 'xa')
-    pb, sb, cb = _src4(xb, 'xb')
+    (a, keep_a), (b, keep_b) = _src4(xa, 'xa'), _src4(xb, 'xb')
     pl = 4 if prec == PREC_BF16X3 else 2
     nbytes = (n * h * w * cin * 4, n * h * w * cout * ((4 if want_y else 0) + (pl if out16 is not None else 0)))
     with _Timed('conv_thin', 2.0 * n * h * w * cout * cin * ksize * ksize, (n, h, w, cin, cout, ksize, 0, 0), nbytes, mm=3 if prec == PREC_BF16X3 else 1):
-        check(_lib.lib().lp_stem8_fwd(pa, None if sa is None else ctypes.addressof(sa), ca, pb, None if sb is None else ctypes.addressof(sb), cb,
-                                      _c_int32(cmap), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(alpha), n, h, w, cin, cout, pack.cols_p,
-                                      pack.rows_p, ksize, prec, _p(o_hi), _p(o_lo), int(bool(out16)), _stream()), 'lp_stem8_fwd')
+        check(_lib.lib().lp_stem8_fwd(*a, *b, _c_int32(cmap), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(alpha), n, h, w, cin, cout,
+                                      pack.cols_p, pack.rows_p, ksize, prec, _p(o_hi), _p(o_lo), int(bool(out16)), _stream()), 'lp_stem8_fwd')
     if out16 is None:
         return y
     return y, Act16(o_hi, o_lo, cout, None)
@@ -449,32 +448,28 @@ def stem8_wgrad(xa: Optional[Tensor], xb: Optional[Tensor], cmap: int, dy: Tenso
                 bias_grad: bool = False):
     """dw [Cout,Cin,k,k] (and db [Cout]) of ``stem8_conv`` from the fp32 gradient dy [N,H,W,Cout]; fp32, the same summation order in every run.
     ``sn`` / ``accum`` as in ``conv_wgrad16``."""
-    import ctypes
     _chk(dy, 'dy')
     n, h, w, cout = dy.shape
     ws = torch.empty(_lib.lib().lp_stem8_wgrad_workspace_bytes(n, h, cout, ksize) // 4, dtype=torch.float32, device=dy.device)
     dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=dy.device)
     db = torch.empty(cout, dtype=torch.float32, device=dy.device) if bias_grad else None
-    pa, sa, ca = _src4(xa, 'xa')
-    pb, sb, cb = _src4(xb, 'xb')
+    (a, keep_a), (b, keep_b) = _src4(xa, 'xa'), _src4(xb, 'xb')
     with _Timed('wgrad_thin', 2.0 * n * h * w * cout * cin * ksize * ksize, (n, h, w, cin, cout, ksize, 0, 0), (n * h * w * (cout + cin) * 4, dw.numel() * 4)):
-        check(_lib.lib().lp_stem8_wgrad(pa, None if sa is None else ctypes.addressof(sa), ca, pb, None if sb is None else ctypes.addressof(sb), cb,
-                                        _c_int32(cmap), dy.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), n, h, w, cin, cout, ksize, _stream()),
-              'lp_stem8_wgrad')
+        check(_lib.lib().lp_stem8_wgrad(*a, *b, _c_int32(cmap), dy.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), n, h, w, cin, cout, ksize,
+                                        _stream()), 'lp_stem8_wgrad')
     dw = _sn_finish(dw, sn, accum)
     return (dw, db) if bias_grad else dw
 
 
 def stem8_dgrad(dy: Tensor, w_orig: Tensor, alpha: Optional[Tensor], cmap: int, cb: int, *, ksize: int) -> Tensor:
     """gradient of ``stem8_conv`` w.r.t. its SECOND source (the image; the stickman has none) -> contiguous N x Cb x H x W; fp32 on fp32 W_orig"""
-    import ctypes
     _chk(dy, 'dy'); _chk(w_orig, 'w_orig')
     n, h, w, cout = dy.shape
     cin = w_orig.shape[1]
     dx = torch.empty((n, cb, h, w), dtype=torch.float32, device=dy.device)
-    st = (ctypes.c_longlong * 4)(*dx.stride())
+    (_, dx_strides, _), keep = _src4(dx, 'dx')
     with _Timed('conv_thin', 2.0 * n * h * w * cout * cb * ksize * ksize, (n, h, w, cout, cb, ksize, 0, 0), (dy.numel() * 4, dx.numel() * 4)):
-        check(_lib.lib().lp_stem8_dgrad(dy.data_ptr(), w_orig.data_ptr(), _p(alpha), dx.data_ptr(), ctypes.addressof(st), cb, _c_int32(cmap), n, h, w,
+        check(_lib.lib().lp_stem8_dgrad(dy.data_ptr(), w_orig.data_ptr(), _p(alpha), dx.data_ptr(), dx_strides, cb, _c_int32(cmap), n, h, w,
                                         cin, cout, ksize, _stream()), 'lp_stem8_dgrad')
     return dx
 

@@ -1037,6 +1037,37 @@ def as_nchw_view(x_nhwc: torch.Tensor) -> torch.Tensor:
     return x_nhwc.permute(0, 3, 1, 2)
 
 
+def cached_pack(packs, wd, mode, prec, small_k=False) -> 'ops.WeightPack':
+    """the mode-``mode`` WeightPack of ``wd``: ``packs`` = a per-step dict cache shared by several calls on the same W_orig (discriminator passes),
+    the cached (forward, dgrad) packs of a frozen w, or None (pack now)"""
+    if isinstance(packs, dict):
+        key = (wd.data_ptr(), mode)
+        if key not in packs:
+            packs[key] = ops.pack_weights(wd, mode, prec, small_k=small_k)
+        return packs[key]
+    return packs[mode] if (packs is not None and mode < 2) else ops.pack_weights(wd, mode, prec, small_k=small_k)
+
+
+def emit_args(emit):
+    """the ``emit`` protocol of the conv Functions, None | (out_relu: 0|1, holder list[, emit_prec | None[, want_y]]) -> (out16, emit_prec, want_y).
+    Planes-only output (want_y False): nothing reads the fp32 y of a conv whose only consumer takes the emitted planes (conv -> ReLU -> conv chains
+    of the critic) -- the autograd edge is carried by a zero-stride phantom of y's shape"""
+    if emit is None:
+        return None, None, True
+    return emit[0], emit[2] if len(emit) > 2 else None, not (len(emit) > 3 and emit[3] is False)
+
+
+def emit_take(emit, out, cout):
+    """``out`` of a conv op called with ``out16`` from ``emit_args`` -> y; the emitted planes go to the holder, their ReLU pattern on the tape"""
+    if emit is None:
+        return out
+    y, o16 = out
+    emit[1].append(o16)
+    if emit[0]:
+        tape_relu(lambda: o16.hi[..., :cout] > 0, True)
+    return y
+
+
 class ConvFn(torch.autograd.Function):
     """y = conv_{k x k, pad k//2}(act(x), w) + bias + res,  act = identity (pro=0) | ReLU (pro=2);  x, res, y NHWC fp32.
     Forward = lp_act_pack (act(x) -> 16-bit operand planes, kept for backward) + lp_conv16_fwd; backward = one lp_act_pack of dY
@@ -1055,16 +1086,8 @@ class ConvFn(torch.autograd.Function):
         assert not reflect or (ksize == 3 and emit is None), 'reflection padding: 3x3 convs without epilogue-emitted planes'
         small_k = ksize == 3 and w.shape[1] <= 32
         wd = w.detach().contiguous()
-        # planes-only output (emit = (relu, holder, emit_prec | None, False)): nothing reads the fp32 y of a conv whose only consumer takes the
-        # emitted planes (conv -> ReLU -> conv chains of the critic) -- the autograd edge is carried by a zero-stride phantom of y's shape
-        want_y = not (emit is not None and len(emit) > 3 and emit[3] is False)
-        if isinstance(packs, dict):          # per-step cache shared by several calls on the same W_orig (discriminator passes)
-            key = (wd.data_ptr(), 0)
-            if key not in packs:
-                packs[key] = ops.pack_weights(wd, 0, prec, small_k=small_k)
-            pack = packs[key]
-        else:
-            pack = packs[0] if packs is not None else ops.pack_weights(wd, 0, prec, small_k=small_k)
+        out16, emit_prec, want_y = emit_args(emit)
+        pack = cached_pack(packs, wd, 0, prec, small_k)
         cin, cout, width = x.shape[3], wd.shape[0], x.shape[2]
         bd = None if bias is None else bias.detach().contiguous()
         alpha = None if sn is None else sn[2][1:]
@@ -1072,29 +1095,18 @@ class ConvFn(torch.autograd.Function):
         thin_w = need_w and not reflect and ops.thin_wgrad_supported(cin, cout, ksize, pro, width)       # the weight gradient will want fp32 x
         a16 = x16
         if a16 is None and pro == 0 and res is None and not reflect and ops.thin_conv_supported(cin, cout, ksize, width):
-            y = ops.thin_conv(x, pack, ksize=ksize, bias=bd, alpha=alpha, prec=prec, out16=None if emit is None else emit[0],
-                              out16_prec=None if emit is None or len(emit) < 3 else emit[2], want_y=want_y)
-            if emit is not None:
-                y, o16 = y
-                emit[1].append(o16)
-                if emit[0]:
-                    tape_relu(lambda: emit[1][-1].hi[..., :cout] > 0, True)
+            y = emit_take(emit, ops.thin_conv(x, pack, ksize=ksize, bias=bd, alpha=alpha, prec=prec, out16=out16, out16_prec=emit_prec, want_y=want_y), cout)
         else:
             if a16 is None:
                 a16 = ops.act_pack(x, pro=pro, prec=prec)
                 if pro == 2:
                     tape_relu(lambda: a16.hi[..., :cin] > 0, True)
             #  the MFMA path emits the consumer planes in its OWN operand mode; another mode is only served by the thin-channel branch
-            assert emit is None or len(emit) < 3 or emit[2] in (None, prec), 'emit_prec differs from the conv\'s operand mode on the MFMA path'
-            y = ops.conv16(a16, pack, ksize=ksize, bias=bd, res=res, alpha=alpha, prec=prec, out16=None if emit is None else emit[0],
-                           want_y=want_y or cout % 8 != 0)
+            assert emit_prec in (None, prec), 'emit_prec differs from the conv\'s operand mode on the MFMA path'
+            y = ops.conv16(a16, pack, ksize=ksize, bias=bd, res=res, alpha=alpha, prec=prec, out16=out16, want_y=want_y or cout % 8 != 0)
             if reflect:
                 ops.reflect_border_fwd(a16, wd, alpha, y, prec=prec)
-            if emit is not None:
-                y, o16 = y
-                emit[1].append(o16)
-                if emit[0]:
-                    tape_relu(lambda: o16.hi[..., :cout] > 0, True)
+            y = emit_take(emit, y, cout)
         if y is None:
             y = phantom((x.shape[0], x.shape[1], x.shape[2], cout), x.device)
         if need_w and not thin_w and a16 is None:
@@ -1128,13 +1140,7 @@ class ConvFn(torch.autograd.Function):
             return d16
         cout, cin, width = dy.shape[3], wd.shape[1], dy.shape[2]
         if ctx.needs_input_grad[0]:
-            if isinstance(packs, dict):
-                key = (wd.data_ptr(), 1)
-                if key not in packs:
-                    packs[key] = ops.pack_weights(wd, 1, prec, small_k=(ksize == 3 and wd.shape[0] <= 32))
-                packT = packs[key]
-            else:
-                packT = packs[1] if packs is not None else ops.pack_weights(wd, 1, prec, small_k=(ksize == 3 and wd.shape[0] <= 32))
+            packT = cached_pack(packs, wd, 1, prec, small_k=(ksize == 3 and wd.shape[0] <= 32))
             alpha = None if sn is None else sn[2][1:]
             if pro != 2 and ops.thin_conv_supported(cout, cin, ksize, width):
                 dx = ops.thin_conv(dy, packT, ksize=ksize, alpha=alpha, prec=prec)
@@ -1203,25 +1209,13 @@ class Stem8Fn(torch.autograd.Function):
         wd = w.detach().contiguous()
         cout, cin = wd.shape[0], wd.shape[1]
         small_k = ksize == 3 and cin <= 32
-        want_y = not (emit is not None and len(emit) > 3 and emit[3] is False)
-        assert emit is None or len(emit) < 3 or emit[2] in (None, prec), 'the planes are emitted in the conv\'s own operand mode'
-        if isinstance(packs, dict):
-            key = (wd.data_ptr(), 0)
-            if key not in packs:
-                packs[key] = ops.pack_weights(wd, 0, prec, small_k=small_k)
-            pack = packs[key]
-        else:
-            pack = packs[0] if packs is not None else ops.pack_weights(wd, 0, prec, small_k=small_k)
+        out16, emit_prec, want_y = emit_args(emit)
+        assert emit_prec in (None, prec), 'the planes are emitted in the conv\'s own operand mode'
+        pack = cached_pack(packs, wd, 0, prec, small_k)
         bd = None if bias is None else bias.detach().contiguous()
         alpha = None if sn is None else sn[2][1:]
         xa, xb = xa.detach(), xb.detach()
-        y = ops.stem8_conv(xa, xb, cmap, pack, ksize=ksize, cin=cin, bias=bd, alpha=alpha, prec=prec, out16=None if emit is None else emit[0],
-                           want_y=want_y)
-        if emit is not None:
-            y, o16 = y
-            emit[1].append(o16)
-            if emit[0]:
-                tape_relu(lambda: o16.hi[..., :cout] > 0, True)
+        y = emit_take(emit, ops.stem8_conv(xa, xb, cmap, pack, ksize=ksize, cin=cin, bias=bd, alpha=alpha, prec=prec, out16=out16, want_y=want_y), cout)
         if y is None:
             y = phantom((xb.shape[0], xb.shape[2], xb.shape[3], cout), xb.device)
         ctx.xa, ctx.xb, ctx.wd = xa, xb, wd
@@ -1299,12 +1293,7 @@ class ConvPoolFn(torch.autograd.Function):
         wd = w.detach().contiguous()
 
         def pk(mode):
-            if isinstance(packs, dict):
-                key = (wd.data_ptr(), mode)
-                if key not in packs:
-                    packs[key] = ops.pack_weights(wd, mode, prec)
-                return packs[key]
-            return ops.pack_weights(wd, mode, prec)
+            return cached_pack(packs, wd, mode, prec)
         bd = None if bias is None else bias.detach().contiguous()
         alpha = None if sn is None else sn[2][1:]
         out = ops.conv16(x16, pk(4), ksize=3, bias=bd, res=res, alpha=alpha, prec=prec, phase_dgrad=True,
