@@ -362,6 +362,19 @@ int lp_pool_grad_pack(const float* dy, const float* ymask, float* dm, uint16_t* 
 int lp_head_fwd(const float* z, float* t, float* fake_rgbs, float* fake_segm, int N, int H, int W, void* stream);
 int lp_head_bwd(const float* t, const float* d_rgbs, const float* d_segm, float* dz, int N, int H, int W, float* amax_slots, void* stream);
 
+/* Plain tanh head of the stickman-to-image generator (generators/FSTH.py:82-89,197): fake_rgbs = tanh(z[..., :3]) -- lp_head_fwd/bwd without the
+ * mask composition.  z/t/dz NHWC [N][H][W][Cz], Cz = 3 | 4 (a fourth channel is launch padding of the 3-row head conv: never read as a value, its t
+ * and dz are exact zeros); fake_rgbs / d_rgbs NCHW [N][3][H][W]; t NULL: not kept.  dz[..., c] = d_rgbs[n][c][h][w] * (1 - t^2); amax_slots as in
+ * lp_head_bwd.  Another Cz: LP_ERR_UNSUPPORTED. */
+int lp_tanh_head_fwd(const float* z, float* t, float* fake_rgbs, int N, int H, int W, int Cz, void* stream);
+int lp_tanh_head_bwd(const float* t, const float* d_rgbs, float* dz, int N, int H, int W, int Cz, float* amax_slots, void* stream);
+
+/* Batch-shared affine gradients of nn.InstanceNorm2d(affine=True) (blocks.py:58-60): out_gamma[c] (+)= sum_n dgamma[n][c], out_beta[c] (+)= sum_n
+ * dbeta[n][c] over the per-sample rows lp_adain_relu_bwd(_planes) wrote (row stride ab_stride floats), fp32, rows added in the order 0 .. N-1 -- the
+ * same bits on every run.  accumulate != 0: added to what out_gamma / out_beta hold (the parameters' .grad); 0: written. */
+int lp_norm_affine_grad(const float* dgamma, const float* dbeta, int ab_stride, float* out_gamma, float* out_beta, int N, int C, int accumulate,
+                        void* stream);
+
 /* ---- discriminator / perceptual-loss helpers (discriminators/no_landmarks.py:52-108, criterions/common/perceptual_loss.py) ---- */
 /* dx = dA * [x > 0]                       (autograd of nn.ReLU, blocks.py:71-73,84) */
 int lp_relu_bwd(const float* dA, const float* x, float* dx, long long numel, void* stream);

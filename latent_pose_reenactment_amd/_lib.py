@@ -111,6 +111,9 @@ SIGNATURES = {
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'lp_head_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'lp_tanh_head_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'lp_tanh_head_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'lp_norm_affine_grad': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'lp_relu_bwd': (_i, [_vp, _vp, _vp, _ll, _vp]),
     'lp_avgpool2_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     'lp_avgpool2_fwd16': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -1064,6 +1064,45 @@ def head_bwd(t: Tensor, d_rgbs: Tensor, d_segm: Optional[Tensor], amax: bool = F
     return dz
 
 
+def tanh_head_fwd(z: Tensor, want_t: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    """z [N,H,W,Cz], Cz = 3 | 4 (a fourth channel is launch padding) -> (tanh(z) NHWC | None, fake_rgbs NCHW [N,3,H,W] = tanh(z[..., :3])):
+    the head of generators/FSTH.py -- no mask, no range shift."""
+    _chk(z, 'z')
+    n, h, w, cz = z.shape
+    t = torch.empty_like(z) if want_t else None
+    rgbs = torch.empty((n, 3, h, w), dtype=torch.float32, device=z.device)
+    check(_lib.lib().lp_tanh_head_fwd(z.data_ptr(), _p(t), rgbs.data_ptr(), n, h, w, cz, _stream()), 'lp_tanh_head_fwd')
+    return t, rgbs
+
+
+def tanh_head_bwd(t: Tensor, d_rgbs: Tensor, amax: bool = False) -> Tensor:
+    """dz [N,H,W,Cz] = d_rgbs (NCHW) * (1 - t^2), an exact zero in a padding channel"""
+    _chk(t, 't'); _chk(d_rgbs, 'd_rgbs')
+    n, h, w, cz = t.shape
+    assert d_rgbs.shape == (n, 3, h, w), (d_rgbs.shape, t.shape)
+    dz = torch.empty_like(t)
+    check(_lib.lib().lp_tanh_head_bwd(t.data_ptr(), d_rgbs.data_ptr(), dz.data_ptr(), n, h, w, cz, _p(_amax_attach(dz, amax)), _stream()), 'lp_tanh_head_bwd')
+    return dz
+
+
+def norm_affine_grad(dgamma: Tensor, dbeta: Tensor, accum_gamma: Optional[Tensor] = None, accum_beta: Optional[Tensor] = None):
+    """per-sample (dgamma, dbeta) [N,C] rows of ``adain_relu_bwd`` -> the gradients [C] of a batch-shared gamma / beta (nn.InstanceNorm2d(affine=True)),
+    rows added in a fixed order.  ``accum_gamma`` / ``accum_beta`` (the parameters' .grad, both or neither): added to in place -> (None, None)."""
+    n, c = dgamma.shape
+    assert dbeta.shape == (n, c) and dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.is_cuda and dbeta.is_cuda
+    assert dgamma.stride(1) == 1 and dbeta.stride(1) == 1 and dgamma.stride(0) == dbeta.stride(0)
+    assert (accum_gamma is None) == (accum_beta is None)
+    accumulate = accum_gamma is not None
+    if accumulate:
+        og, ob = accum_gamma, accum_beta
+        assert all(t.is_contiguous() and t.dtype == torch.float32 and t.numel() == c and t.is_cuda for t in (og, ob))
+    else:
+        og, ob = (torch.empty(c, dtype=torch.float32, device=dgamma.device) for _ in range(2))
+    check(_lib.lib().lp_norm_affine_grad(dgamma.data_ptr(), dbeta.data_ptr(), dgamma.stride(0), og.data_ptr(), ob.data_ptr(), n, c, int(accumulate),
+                                         _stream()), 'lp_norm_affine_grad')
+    return (None, None) if accumulate else (og, ob)
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)

@@ -528,10 +528,13 @@ RAW16_SKIP = os.environ.get('LP_G_RAW16', '1') != '0'      # conv2's epilogue al
 
 class _DecoderFunction(torch.autograd.Function):
     """inputs: affine [B, n_aff] (projector output; per AdaIN: C biases then C weights, noBottleneck.py:108-125),
-    constant [1,C,s,s], then per block (w1, w2[, w_skip, b_skip]) and (w_head, b_head) -- the W_ORIG parameters themselves: 1/sigma of each
+    constant [1,C,s,s] -- or a per-sample input [B,C,s,s] (the encoder output of generators/FSTH.py: its gradient comes back un-summed) --,
+    then per block (w1, w2[, w_skip, b_skip]) and (w_head, b_head) -- the W_ORIG parameters themselves: 1/sigma of each
     conv (``cfg['sn']``, from SNBatch) is the ``alpha`` of its launch's epilogue, W/sigma is never formed, and the weight-gradient launches
     return the gradient w.r.t. W_orig through the legacy-hook rule (``snw``).
-    outputs: fake_rgbs [B,3,S,S], fake_segm [B,1,S,S] (NCHW, noBottleneck.py:170-181)."""
+    outputs: fake_rgbs [B,3,S,S], fake_segm [B,1,S,S] (NCHW, noBottleneck.py:170-181).
+    ``cfg['head_pad']`` = (w4, b4): the head is the plain tanh of generators/FSTH.py -- a 3-row conv (w_head [3,C,3,3]) launched zero-padded to the 4
+    rows the head kernels are built for (w4 / b4 hold the padded copies), fake_rgbs = tanh(z[..., :3]) (lp_tanh_head_*), fake_segm None."""
 
     @staticmethod
     def forward(ctx, cfg, affine, constant, *weights):
@@ -641,12 +644,18 @@ class _DecoderFunction(torch.autograd.Function):
         gh, bh, oh = aff(ch)
         sth = in_stats(x, x_cs, gh, bh)
         wh, bhd = wl[wi], wl[wi + 1]
+        head_pad = cfg.get('head_pad')
+        if head_pad is not None:
+            wh, bhd = head_pad
         ph = fpack(wi, wh)
         ah = norm_planes(x, sth)
         z = ops.conv16(ah, ph, ksize=3, bias=bhd.detach().contiguous(), alpha=sn[wi][2][1:], prec=prec)
         if cfg.get('debug') is not None:
             cfg['debug'].setdefault('relu_planes', []).append(ah.hi)
-        t, rgbs, segm = ops.head_fwd(z, want_t=need_grad)
+        if head_pad is not None:
+            (t, rgbs), segm = ops.tanh_head_fwd(z, want_t=need_grad), None
+        else:
+            t, rgbs, segm = ops.head_fwd(z, want_t=need_grad)
         if need_grad:
             ctx.cfg = cfg
             ctx.saved = saved
@@ -686,19 +695,30 @@ class _DecoderFunction(torch.autograd.Function):
 
         x, sth, oh, t, ah = ctx.head
         ch = blocks[-1][1]
-        dz = ops.head_bwd(t, d_rgbs.contiguous(), None if d_segm is None else d_segm.contiguous(), amax=f16)
+        head_pad = cfg.get('head_pad')
+        if head_pad is not None:
+            dz = ops.tanh_head_bwd(t, d_rgbs.contiguous(), amax=f16)
+        else:
+            dz = ops.head_bwd(t, d_rgbs.contiguous(), None if d_segm is None else d_segm.contiguous(), amax=f16)
         wi = len(wl) - 2
+        # (tanh head: the launch is the padded 4-row one; the raw gradient's rows 0..2 then take the spectral-norm rule of the [3, C, 3, 3] parameter)
+        hsn, haccum = (None, None) if head_pad is not None else (snw(wi), _accum_target(params[wi]))
         if ops.thin_wgrad_supported(ch, dz.shape[3], 3, 1, dz.shape[2]):
             thin = ops.thin_wgrad16 if isinstance(x, ops.Act16) else ops.thin_wgrad
-            grads[wi], grads[wi + 1] = thin(x, dz, ksize=3, pro=1, scale=sth[2], shift=sth[3], sn=snw(wi),
-                                            accum=_accum_target(params[wi]), bias_grad=True)
+            grads[wi], grads[wi + 1] = thin(x, dz, ksize=3, pro=1, scale=sth[2], shift=sth[3], sn=hsn, accum=haccum, bias_grad=True)
         else:
-            grads[wi], grads[wi + 1] = ops.conv_wgrad16(ah, ops.act_pack(dz, prec=prec, grad=True), ksize=3, prec=prec, sn=snw(wi),
-                                                        accum=_accum_target(params[wi]), bias_grad=True)
+            grads[wi], grads[wi + 1] = ops.conv_wgrad16(ah, ops.act_pack(dz, prec=prec, grad=True), ksize=3, prec=prec, sn=hsn, accum=haccum, bias_grad=True)
+        if head_pad is not None:
+            rows = wl[wi].shape[0]
+            grads[wi] = ops.sn_grad_apply(grads[wi][:rows].contiguous(), wl[wi].contiguous(), *sn[wi], accum=_accum_target(params[wi]))
+            grads[wi + 1] = grads[wi + 1][:rows].contiguous()
         packsT = cfg.get('packsT')        # dgrad packs from the same batched launch (training), else packed on demand
 
         def tpack(i, small_k=False, phase=False, prec=prec):
-            return packsT[i] if packsT is not None else ops.pack_weights(wl[i].contiguous(), 3 if phase else 1, prec, small_k=small_k)
+            if packsT is not None:
+                return packsT[i]
+            src = head_pad[0] if (head_pad is not None and i == len(wl) - 2) else wl[i]
+            return ops.pack_weights(src.contiguous(), 3 if phase else 1, prec, small_k=small_k)
         pT = tpack(wi, small_k=True)
         dA = ops.conv(dz, pT, ksize=3, alpha=sn[wi][2][1:], prec=prec, grad=True)
         g, dg, db = slices(oh, ch)
@@ -770,7 +790,10 @@ class _DecoderFunction(torch.autograd.Function):
                 dx = ops.adain_relu_bwd(dA0, x, dx_skip, g, st0[0], st0[1], st0[2], st0[3], dg, db, up_bwd, amax=pnext == PREC_F16 and bi > 0)
             if dbg is not None:
                 dbg[f'dx{bi}'] = dx; dbg[f'dh1_{bi}'] = dh1; dbg[f'dxskip{bi}'] = dx_skip
-        d_const = dx.sum(dim=0, keepdim=True).permute(0, 3, 1, 2).contiguous()
+        if ctx.const_shape[0] != 1:          # a per-sample input: its gradient as it is (an NHWC-stored view, like the input)
+            d_const = dx.permute(0, 3, 1, 2)
+        else:
+            d_const = dx.sum(dim=0, keepdim=True).permute(0, 3, 1, 2).contiguous()
         return (None, d_affine, d_const, *grads)
 
 
@@ -1076,8 +1099,10 @@ class ConvFn(torch.autograd.Function):
     thin-channel kernels.  ``packs`` = optional cached (forward, dgrad) WeightPacks of a frozen w."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, res, ksize, pro, prec, packs, sn=None, x16=None, emit=None, reflect=False):
+    def forward(ctx, x, w, bias, res, ksize, pro, prec, packs, sn=None, x16=None, emit=None, reflect=False, stats=None):
         """``sn`` = (u_used, v_used, [sigma, 1/sigma]) from SNBatch when ``w`` is a spectrally normalised W_orig.
+        ``stats`` (a list; MFMA path without ``emit`` / ``reflect``): the epilogue also leaves the norm-statistics partials of y; the list receives
+        the ``ConvStats`` (None where the launch geometry has no fused statistics).
         ``x16``: operand planes of act(x) that already exist (emitted by the producer conv's epilogue, or packed once for several
         consumers) -- skips this call's lp_act_pack.  ``emit`` = (out_relu: 0|1, holder list): the conv epilogue also writes the
         operand planes of (relu?)(y) for the consumer conv; they are appended to ``holder``.  ``reflect``: the 3x3 conv sits behind
@@ -1103,7 +1128,12 @@ class ConvFn(torch.autograd.Function):
                     tape_relu(lambda: a16.hi[..., :cin] > 0, True)
             #  the MFMA path emits the consumer planes in its OWN operand mode; another mode is only served by the thin-channel branch
             assert emit_prec in (None, prec), 'emit_prec differs from the conv\'s operand mode on the MFMA path'
-            y = ops.conv16(a16, pack, ksize=ksize, bias=bd, res=res, alpha=alpha, prec=prec, out16=out16, want_y=want_y or cout % 8 != 0)
+            if stats is not None:
+                assert emit is None and not reflect, 'epilogue statistics: plain convs only'
+                y, cs = ops.conv16(a16, pack, ksize=ksize, bias=bd, res=res, alpha=alpha, prec=prec, stats=True)
+                stats.append(cs)
+            else:
+                y = ops.conv16(a16, pack, ksize=ksize, bias=bd, res=res, alpha=alpha, prec=prec, out16=out16, want_y=want_y or cout % 8 != 0)
             if reflect:
                 ops.reflect_border_fwd(a16, wd, alpha, y, prec=prec)
             y = emit_take(emit, y, cout)
@@ -1168,18 +1198,20 @@ class ConvFn(torch.autograd.Function):
             db = dy.sum(dim=(0, 1, 2))
         if has_res and ctx.needs_input_grad[3]:
             dres = dy
-        return dx, dw, db, dres, None, None, None, None, None, None, None, None
+        return dx, dw, db, dres, None, None, None, None, None, None, None, None, None
 
 
-def hip_conv(x, w, bias=None, res=None, ksize=3, pro=0, prec=None, packs=None, sn=None, x16=None, emit16=None, emit_prec=None, want_y=True, reflect=False):
+def hip_conv(x, w, bias=None, res=None, ksize=3, pro=0, prec=None, packs=None, sn=None, x16=None, emit16=None, emit_prec=None, want_y=True, reflect=False,
+             stats=None):
     """``x16``: existing operand planes of act(x); ``emit16`` = 0 | 1: also return the operand planes of y (1: of relu(y)), written
     by the conv's epilogue -> ``(y, Act16)``; ``emit_prec``: their operand mode when the consumer's differs from this conv's ``prec``
     (thin-channel first layers only).  ``want_y=False`` (with ``emit16``): the returned y is a PHANTOM (shape and autograd edge only, no
-    storage) -- for convs whose fp32 output nobody reads.  ``reflect``: reflection instead of zero padding (3x3, no ``emit16``)."""
+    storage) -- for convs whose fp32 output nobody reads.  ``reflect``: reflection instead of zero padding (3x3, no ``emit16``).
+    ``stats`` (a list, without ``emit16``): receives the norm-statistics partials the conv's epilogue left (``ConvFn.forward``)."""
     prec = default_prec() if prec is None else prec
     _TAPE_GRAD[0] = torch.is_grad_enabled()
     if emit16 is None:
-        return ConvFn.apply(x, w, bias, res, ksize, pro, prec, packs, sn, x16, None, reflect)
+        return ConvFn.apply(x, w, bias, res, ksize, pro, prec, packs, sn, x16, None, reflect, stats)
     holder = []
     y = ConvFn.apply(x, w, bias, res, ksize, pro, prec, packs, sn, x16, (int(emit16), holder) + ((() if emit_prec is None else (emit_prec,)) if want_y else (emit_prec, False)))
     return y, holder[0]
