@@ -485,6 +485,16 @@ int lp_stem8_dgrad(const float* dy, const float* w, const float* alpha, float* d
  * lp_image_prep_bwd: dx NCHW = g NHWC / std[c] / 2. */
 int lp_image_prep_fwd(const float* x, const float* mean, const float* stdv, float* out, int N, int HW, void* stream);
 int lp_image_prep_bwd(const float* g, const float* stdv, float* dx, int N, int HW, void* stream);
+/* (additive, ABI 12) Stickman rasteriser of the keypoint-driven family (dataloaders/synthetic_voxceleb2_stickmen.draw_stickman on the device):
+ * points [N][P][2] (x, y) in [0, 1] -> out [N][3][S][S] fp32 NCHW, contiguous.  With p = points * (S - 1) and pixel (x, y) = (column, row), every
+ * segment (a, b) of a part gives t = clamp(<pix - a, b - a> / max(|b - a|^2, 1e-12), 0, 1), d = |pix - (a + t (b - a))|; a part's line is
+ * clamp(1 - min d / width, 0, 1) and out[c] = max(0, max over parts of line * colour[part][c]).  The polyline table is the caller's:
+ * seg [L][2] point indices (the segments of one part are consecutive; indices outside 0 .. P-1 are clamped, not reported), part_end [parts] the
+ * exclusive end of each part's run in seg (part_end[parts-1] == L), colour [parts][3]; all DEVICE arrays.  Points are neither clamped nor checked.
+ * One launch, no atomics (bit-reproducible), no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer, N < 1, P or L outside 1 .. 256, parts outside 1 .. 16, S < 1, width <= 0 -- checked before any device work. */
+int lp_stickman_render(const float* points, int N, int P, const int* seg, const int* part_end, const float* colour, int L, int parts, int S,
+                       float width, float* out, void* stream);
 
 /* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per

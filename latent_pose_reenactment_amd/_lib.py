@@ -107,6 +107,7 @@ SIGNATURES = {
     'lp_stem8_dgrad': (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     'lp_image_prep_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'lp_image_prep_bwd': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    'lp_stickman_render': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     'lp_pool_grad_pack': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -59,12 +59,18 @@ def draw_stickman(points, size, width=None):
     return img
 
 
+def sample_keypoints(index, num_frames, seed):
+    """the keypoints of sample ``index``: (encoder frames [K, 68, 2], target frame [68, 2]), drawn in this order from the sample's own stream -- shared
+    with dataloaders/synthetic_voxceleb2_keypoints.py, which hands them out undrawn"""
+    g = torch.Generator().manual_seed(seed * 1000003 + index + 500009)     # (its own stream: the base sample stays what synthetic_voxceleb2 gives)
+    enc_pts = torch.stack([face_keypoints(g) for _ in range(num_frames)])
+    return enc_pts, face_keypoints(g)
+
+
 def make_sample(index, image_size, num_frames, num_labels, finetune, seed):
     data, target = _base.make_sample(index, image_size, num_frames, num_labels, finetune, seed)
-    g = torch.Generator().manual_seed(seed * 1000003 + index + 500009)     # (its own stream: the base sample stays what synthetic_voxceleb2 gives)
-    enc = torch.stack([draw_stickman(face_keypoints(g), image_size) for _ in range(num_frames)])
-    dec_pts = face_keypoints(g)
-    data['enc_stickmen'] = enc
+    enc_pts, dec_pts = sample_keypoints(index, num_frames, seed)
+    data['enc_stickmen'] = torch.stack([draw_stickman(p, image_size) for p in enc_pts])
     data['dec_stickmen'] = draw_stickman(dec_pts, image_size)[None]
     data['dec_keypoints'] = dec_pts.reshape(1, 136)
     return data, target

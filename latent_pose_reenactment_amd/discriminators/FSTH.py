@@ -6,10 +6,11 @@ The critic of discriminators/no_landmarks.py -- same blocks, three passes, ``pre
     keys are ``down_block.1.*`` / ``down_block.4.*``;
   * the reference concatenates the 4-D tensors on dim 2 (rows) and views the result as b x 6 x h x w (FSTH.py:153-158): stickman and image planes
     end up INTERLEAVED over the channels (s0, r0, s1, r1, s2, r2) -- ``fsth.interleaved_order``;
-  * the stickman is a constant for autograd and is shared by the fake and the real passes; pass 2 sees the detached image (inherited).
+  * the stickman is a constant for autograd and is shared by the fake and the real passes; pass 2 sees the detached image (inherited);
+  * a batch without ``dec_stickmen`` has its stickman rendered on the device from ``dec_keypoints`` (fsth.stickmen).
 ``--dis_padding reflection`` would also reflect-pad the stem here; it is refused at construction instead of being run with zero padding."""
 from latent_pose_reenactment_amd.discriminators import no_landmarks as _base
-from latent_pose_reenactment_amd.fsth import TwoSourceStem, interleaved_order, refuse_reflection
+from latent_pose_reenactment_amd.fsth import TwoSourceStem, interleaved_order, refuse_reflection, stickmen
 
 
 class Wrapper(_base.Wrapper):
@@ -29,13 +30,15 @@ class Discriminator(TwoSourceStem, _base.Discriminator):
                          image_size, num_labels)
 
     def _take_stick(self, data_dict):
-        stick = data_dict['dec_stickmen']
+        """the target pose of the coming passes: ``dec_stickmen``, else rendered from ``dec_keypoints`` at the size of the image it stands beside
+        (fsth.stickmen; rendered per call and never stored in ``data_dict``)"""
+        stick = stickmen(data_dict, 'dec', data_dict['target_rgbs'].shape[-1])
         if stick.dim() > 4:
             stick = stick[:, 0]
         self._set_stick(stick)
 
     def start_real_pass(self, data_dict):
-        if data_dict.get('dec_stickmen') is None:
+        if data_dict.get('target_rgbs') is None or (data_dict.get('dec_stickmen') is None and data_dict.get('dec_keypoints') is None):
             return
         self._take_stick(data_dict)
         super().start_real_pass(data_dict)

@@ -26,6 +26,23 @@ def interleaved_order(cs, cr):
     return [(j % 2, j // 2) for j in range(2 * cs)]
 
 
+def stickmen(data_dict, which, size):
+    """the ``which`` ('enc' | 'dec') stickmen of a batch, B x K x 3 x S x S: ``<which>_stickmen`` when the batch carries them (no launch), else rendered
+    on the device from ``<which>_keypoints`` B x K x 136 (hipops.stickman_render, one launch on the current stream).
+    The render is NOT written back into ``data_dict``: GraphedTrainStep runs its eager warm-up steps on the dict it then captures with -- a stickman
+    cached by the first warm-up step would be found by the next, the render would never be captured and every replay would see a stale pose.  Each
+    consumer renders what it reads instead; there is no cache to invalidate."""
+    if which not in ('enc', 'dec'):
+        raise ValueError(f"stickmen: which must be 'enc' or 'dec', got {which!r}")
+    stick = data_dict.get(f'{which}_stickmen')
+    if stick is not None:
+        return stick
+    points = data_dict.get(f'{which}_keypoints')
+    if points is None:
+        raise KeyError(f"the batch carries neither '{which}_stickmen' nor '{which}_keypoints'")
+    return ops.stickman_render(points, size)
+
+
 class TwoSourceStem:
     """mixin of a ``ResTrunk`` whose stem reads (stickman, image): ``_set_stick`` names the stickman of the coming passes; ``_trunk`` is then called
     with the image alone, as in the RGB critic.  Without a stickman set the stem is the plain one."""
@@ -123,7 +140,7 @@ class ConvEmbedder(TwoSourceStem, _critic.ResTrunk):
         b, k, c, h, w = rgbs.shape
         x = rgbs.reshape(b * k, c, h, w)
         if self.with_stickman:
-            stick = data_dict['enc_stickmen']
+            stick = stickmen(data_dict, 'enc', h)
             self._set_stick(stick.reshape(b * k, stick.shape[2], h, w))
         self.__dict__['_step_packs'] = self._fresh_packs()          # new step: the optimizer has changed W_orig
         layers = self._conv_sn_layers()

@@ -19,7 +19,7 @@ from torch import nn
 
 from . import hipops as ops
 from . import nn as lpnn
-from .fsth import refuse_reflection
+from .fsth import refuse_reflection, stickmen
 from .nn import (ADAIN_EPS, SN_EPS_CONV, AvgPool2Fn, ConvPoolFn, Generator, SNBatch, SNLinearFn, SNWeight, _DecoderFunction, _Indexed, _accum_target,
                  as_nchw_view, hip_conv, phantom, to_nhwc)
 from ._lib import PREC_F16
@@ -112,11 +112,13 @@ MIN_BOTTLENECK = 4
 class GeneratorFSTH(Generator):
     """Drop-in for generators/FSTH.py::Generator of the reference: same constructor arguments, state-dict keys and order, ``named_parameters()``
     order, ``get_num_affine_params``, ``enable_finetuning`` and ``forward(data_dict)`` contract (reads ``embeds`` and ``dec_stickmen``, writes
-    ``fake_rgbs`` only).  Operand mode: ``nn.generator_prec()`` for encoder and decoder alike."""
+    ``fake_rgbs`` only).  A batch without ``dec_stickmen`` has them rendered on the device from ``dec_keypoints`` at ``image_size`` (fsth.stickmen).
+    Operand mode: ``nn.generator_prec()`` for encoder and decoder alike."""
 
     def __init__(self, padding, in_channels, out_channels, num_channels, max_num_channels, embed_channels, norm_layer, gen_num_downsample_blocks,
-                 gen_num_residual_blocks, prec=None):
+                 gen_num_residual_blocks, prec=None, image_size=None):
         nn.Module.__init__(self)
+        self.image_size = image_size          # side of the stickman rendered for a batch that carries ``dec_keypoints`` only
         refuse_reflection(padding, '--gen_padding')
         if norm_layer != 'in':
             raise NotImplementedError(f"--norm_layer {norm_layer}: the FSTH generator on the HIP path implements norm_layer 'in' only")
@@ -336,7 +338,10 @@ class GeneratorFSTH(Generator):
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------------------
     def forward(self, data_dict):
-        stick = data_dict['dec_stickmen']
+        if data_dict.get('dec_stickmen') is None and data_dict.get('dec_keypoints') is not None and self.image_size is None:
+            raise RuntimeError('a batch with dec_keypoints only needs the frame size to render at: construct the generator with image_size '
+                               '(generators/FSTH.py passes --image_size)')
+        stick = stickmen(data_dict, 'dec', self.image_size)
         if stick.dim() > 4:
             stick = stick[:, 0]
         if not (stick.is_cuda and next(self.parameters()).is_cuda):

@@ -8,6 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import PREC_BF16, PREC_BF16X3, PREC_F16, check
+from .dataloaders.synthetic_voxceleb2_stickmen import PARTS      # the one place that knows the face topology (stickman_render's default table)
 
 Tensor = torch.Tensor
 
@@ -1101,6 +1102,87 @@ def norm_affine_grad(dgamma: Tensor, dbeta: Tensor, accum_gamma: Optional[Tensor
     check(_lib.lib().lp_norm_affine_grad(dgamma.data_ptr(), dbeta.data_ptr(), dgamma.stride(0), og.data_ptr(), ob.data_ptr(), n, c, int(accumulate),
                                          _stream()), 'lp_norm_affine_grad')
     return (None, None) if accumulate else (og, ob)
+
+
+def stickman_table(parts=PARTS):
+    """polyline table of lp_stickman_render from ``parts`` = ((first point, last point, closed, RGB colour), ...) -> (seg [L][2] point indices with the
+    segments of one part consecutive and a closed part's closing edge last, part_end [parts] exclusive ends of the runs, colour [parts][3], number of
+    points the table names); host lists, checked here: non-empty runs, indices >= 0, the kernel's limits of 256 segments and 16 parts"""
+    seg, part_end, colour = [], [], []
+    for first, last, closed, rgb in parts:
+        idx = list(range(int(first), int(last) + 1))
+        pairs = list(zip(idx[:-1], idx[1:])) + ([(idx[-1], idx[0])] if closed else [])
+        if first < 0 or not pairs:
+            raise ValueError(f'stickman part ({first}, {last}, closed={closed}) has no segment or a negative point index')
+        if len(rgb) != 3:
+            raise ValueError(f'stickman part ({first}, {last}): the colour must be an RGB triple, got {rgb}')
+        seg += [list(p) for p in pairs]
+        part_end.append(len(seg))
+        colour.append([float(c) for c in rgb])
+    if not 1 <= len(part_end) <= 16 or len(seg) > 256:
+        raise ValueError(f'stickman table with {len(part_end)} parts and {len(seg)} segments: 1 .. 16 parts and at most 256 segments are supported')
+    assert part_end[-1] == len(seg)
+    return seg, part_end, colour, 1 + max(max(p) for p in seg)
+
+
+_STICKMAN_TABLES = {}
+
+
+def _stickman_device_table(parts, device):
+    """``stickman_table`` on ``device``, built once per (parts, device): three small tensors that every later launch (and graph replay) reads"""
+    parts = tuple((int(f), int(l), bool(c), tuple(float(v) for v in rgb)) for f, l, c, rgb in parts)
+    key = (parts, device)
+    tab = _STICKMAN_TABLES.get(key)
+    if tab is None:
+        seg, part_end, colour, npoints = stickman_table(parts)
+        tab = (torch.tensor(seg, dtype=torch.int32).to(device), torch.tensor(part_end, dtype=torch.int32).to(device),
+               torch.tensor(colour, dtype=torch.float32).to(device), len(seg), len(part_end), npoints)
+        _STICKMAN_TABLES[key] = tab
+    return tab
+
+
+def stickman_render(points: Tensor, size: int, width: Optional[float] = None, out: Optional[Tensor] = None, parts=PARTS) -> Tensor:
+    """keypoints [..., P, 2] or [..., 2P] ((x, y) pairs in [0, 1]; fp32, on the GPU) -> stickmen [..., 3, S, S]: ``draw_stickman`` of
+    dataloaders/synthetic_voxceleb2_stickmen.py as ONE launch on the current stream (lp_stickman_render).  ``width`` defaults to max(1, S / 64).
+    ``out``: a contiguous fp32 tensor of the result's shape to write into -- it may be a view of a larger tensor.  Points are neither clamped nor
+    checked (that would need a host sync), as on the host."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise ValueError('stickman_render: the keypoints must be a CUDA tensor (the stickman is rendered on the MI355X; the host renderer is '
+                         'dataloaders.synthetic_voxceleb2_stickmen.draw_stickman)')
+    if points.dtype != torch.float32:
+        raise ValueError(f'stickman_render: fp32 keypoints are required, got {points.dtype}')
+    size = int(size)
+    if size < 1:
+        raise ValueError(f'stickman_render: size must be >= 1, got {size}')
+    width = max(1.0, size / 64.0) if width is None else float(width)
+    if not width > 0:
+        raise ValueError(f'stickman_render: width must be > 0, got {width}')
+    seg, part_end, colour, nseg, nparts, npoints = _stickman_device_table(parts, points.device)
+    if points.dim() >= 2 and points.shape[-1] == 2 and points.shape[-2] >= npoints:
+        lead, p = tuple(points.shape[:-2]), points.shape[-2]
+    elif points.dim() >= 1 and points.shape[-1] % 2 == 0 and points.shape[-1] // 2 >= npoints:
+        lead, p = tuple(points.shape[:-1]), points.shape[-1] // 2
+    else:
+        raise ValueError(f'stickman_render: keypoints {tuple(points.shape)}: expected [..., P, 2] or [..., 2P] with P >= {npoints}, the points the '
+                         'polyline table names')
+    if p > 256:
+        raise ValueError(f'stickman_render: at most 256 keypoints per image are supported, got {p}')
+    n = 1
+    for d in lead:
+        n *= d
+    shape = lead + (3, size, size)
+    if n < 1:
+        raise ValueError(f'stickman_render: keypoints {tuple(points.shape)} hold no image')
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=points.device)
+    elif not (isinstance(out, torch.Tensor) and out.device == points.device and out.dtype == torch.float32 and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise ValueError(f'stickman_render: out must be a contiguous fp32 tensor of shape {shape} on {points.device}, got '
+                         f'{tuple(out.shape)} {out.dtype} {out.device} contiguous={out.is_contiguous()}')
+    pts = points.detach().contiguous()
+    check(_lib.lib().lp_stickman_render(pts.data_ptr(), n, p, seg.data_ptr(), part_end.data_ptr(), colour.data_ptr(), nseg, nparts, size, width,
+                                        out.data_ptr(), _stream()), 'lp_stickman_render')
+    return out
 
 
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
