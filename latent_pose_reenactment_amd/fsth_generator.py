@@ -20,8 +20,8 @@ from torch import nn
 from . import hipops as ops
 from . import nn as lpnn
 from .fsth import refuse_reflection, stickmen
-from .nn import (ADAIN_EPS, SN_EPS_CONV, AvgPool2Fn, ConvPoolFn, Generator, SNBatch, SNLinearFn, SNWeight, _DecoderFunction, _Indexed, _accum_target,
-                 as_nchw_view, hip_conv, phantom, to_nhwc)
+from .nn import (ADAIN_EPS, SN_EPS_CONV, AvgPool2Fn, ConvPoolFn, DecoderArgs, Generator, SNBatch, SNLinearFn, SNWeight, _DecoderFunction, _Indexed,
+                 _accum_target, as_nchw_view, hip_conv, phantom, to_nhwc)
 from ._lib import PREC_F16
 
 
@@ -149,7 +149,7 @@ class GeneratorFSTH(Generator):
         dec[f'_{nb}'] = _AdaSlot(cin)          # nb + 1: ReLU, nb + 2: padding, nb + 3: the head conv, nb + 4: Tanh
         dec[f'_{nb + 3}'] = SNWeight((out_channels, cin, 3, 3), True, SN_EPS_CONV)
         self.decoder_blocks = _Indexed(**dec)
-        self.num_affine_params = sum(2 * (a + b) for a, b, _ in self.blocks_cfg) + 2 * cin
+        self.num_affine_params = lpnn.decoder_layout(self.blocks_cfg, MIN_BOTTLENECK, False).n_affine          # (the same for every input size)
         self.project = SNWeight((self.num_affine_params, embed_channels), True, SN_EPS_CONV)
         self.embed_channels = embed_channels
         self.num_downsample = nd
@@ -165,17 +165,14 @@ class GeneratorFSTH(Generator):
     def _head(self):
         return self.decoder_blocks._modules[str(len(self.blocks_cfg) + 3)]
 
+    def _decoder_in_size(self):
+        """side of the bottleneck map, known from the first forward on"""
+        return self.__dict__['_bott_size']
+
     def _ada_slots(self):
         """the AdaIN layers in module order -- the order the projector's output is consumed in (per layer: C biases, then C weights)"""
         nb = len(self.blocks_cfg)
         return [s for i in range(nb) for s in self.decoder_blocks._modules[str(i)].slots()] + [self.decoder_blocks._modules[str(nb)]]
-
-    def _decoder_sn_layers(self):
-        layers = []
-        for i in range(len(self.blocks_cfg)):
-            c1, c2, sk = self.decoder_blocks._modules[str(i)].convs()
-            layers += [c1, c2] + ([sk] if sk is not None else [])
-        return layers + [self._head()]
 
     def _encoder_sn_layers(self):
         return list(self._stem()) + [l for blk in self.down_blocks._modules.values() for l in blk.sn_layers()]
@@ -188,34 +185,6 @@ class GeneratorFSTH(Generator):
             cached = (self._decoder_sn_layers() + self._encoder_sn_layers() + ([] if self.finetuning else [self.project]), self.finetuning)
             self.__dict__['_sn_layer_cache'] = cached
         return cached
-
-    def _conv_weights(self, states):
-        weights, sn, k = [], [], 0
-        for i in range(len(self.blocks_cfg)):
-            c1, c2, sk = self.decoder_blocks._modules[str(i)].convs()
-            weights += [c1.weight_orig, c2.weight_orig]
-            sn += [states[k], states[k + 1]]
-            k += 2
-            if sk is not None:
-                weights += [sk.weight_orig, sk.bias]
-                sn += [states[k], None]
-                k += 1
-        head = self._head()
-        return weights + [head.weight_orig, head.bias], sn + [states[k], None]
-
-    def _phase_weight_indices(self):
-        size = self.__dict__['_bott_size']
-        cached = self.__dict__.get('_phase_idx')
-        if cached is None or cached[0] != size:
-            idx, wi = set(), 0
-            for cin, cout, up in self.blocks_cfg:
-                size *= 2 if up else 1
-                if lpnn.phase_conv(up, size, False):
-                    idx.add(wi)
-                wi += 4 if (cin != cout or up) else 2
-            cached = (self.__dict__['_bott_size'], idx)
-            self.__dict__['_phase_idx'] = cached
-        return cached[1]
 
     # ---- the 3-row head conv is launched zero-padded to the 4 rows the head kernels take ------------------------------------------------------------
     def _head_pad(self):
@@ -241,10 +210,10 @@ class GeneratorFSTH(Generator):
         states = self._sn_update()
         self.__dict__['_prepared_sn'] = states
         if self.__dict__.get('_bott_size') is not None:
-            weights, sn = self._conv_weights(states)
+            weights, _ = self._conv_weights(states)
             if any(w.requires_grad for w in weights):
                 pad = self._head_pad()
-                self.__dict__['_prepared_packs'] = (pad, self._train_packs_update(self._pack_sources(weights, pad), sn))
+                self.__dict__['_prepared_packs'] = (pad, self._train_packs_update(self._pack_sources(weights, pad)))
 
     # ---- projector / fine-tuning ----------------------------------------------------------------------------------------------------------------
     def enable_finetuning(self, data_dict=None):
@@ -357,7 +326,7 @@ class GeneratorFSTH(Generator):
         affine = self._affine(data_dict, stick.shape[0], states)
         weights, sn = self._conv_weights(states)
         enc_layers = self._encoder_sn_layers()
-        nd = len(self._decoder_sn_layers())
+        nd = len(self._layout().conv_idx)
         sn_of = {id(l): s for l, s in zip(enc_layers, states[nd:nd + len(enc_layers)])}
         need_grad = torch.is_grad_enabled() and (affine.requires_grad or any(p.requires_grad for p in self.parameters()))
         prec = self.prec if need_grad else self.infer_prec
@@ -365,27 +334,14 @@ class GeneratorFSTH(Generator):
         prepared = self.__dict__.pop('_prepared_packs', None)
         if not torch.is_grad_enabled():
             prepared = None
-        packs = packsT = None
         pad = prepared[0] if prepared is not None else self._head_pad()
-        if need_grad and self.training:
-            packs, packsT = prepared[1] if prepared is not None else self._train_packs_update(self._pack_sources(weights, pad), sn)
-        if not need_grad and not self.training:          # inference: the decoder's weights are packed once (Generator.forward)
-            from .optim import WEIGHTS_GENERATION
-            key = (prec, self._bott_size, WEIGHTS_GENERATION[0]) + tuple((w.data_ptr(), w._version) for w in weights)
-            cache = self.__dict__.get('_pack_cache')
-            if cache is None or cache[0] != key:
-                ph = self._phase_weight_indices()
-                src = self._pack_sources(weights, pad)
-                cache = (key, [ops.pack_weights(w.detach().contiguous(), 2 if i in ph else 0, prec) if s_ is not None else None
-                               for i, (w, s_) in enumerate(zip(src, sn))])
-                self.__dict__['_pack_cache'] = cache
-            packs = cache[1]
+        packs, packsT = self._decoder_packs(weights, self._pack_sources(weights, pad), prec, precs, need_grad, None if prepared is None else prepared[1])
         debug = getattr(self, '_debug', None)
         x = self._encode(stick, sn_of, prec, self._encoder_packs(need_grad and self.training), debug)
         # identity-skip blocks add their fp32 input: residual blocks on maps the 16-bit-resident outputs would cover switch those outputs off
         res_blocks = any(not up for _, _, up in self.blocks_cfg)
         y16 = lpnn.G_Y16 and self.training and need_grad and not (res_blocks and self._bott_size >= lpnn.Y16_MIN_MAP)
-        cfg = dict(blocks=self.blocks_cfg, prec=prec, precs=precs, need_grad=need_grad, sn=sn, packs=packs, packsT=packsT, debug=debug, y16=y16,
-                   reflect=False, head_pad=pad)
+        cfg = DecoderArgs(layout=self._layout(), prec=prec, precs=precs, need_grad=need_grad, sn=sn, packs=packs, packsT=packsT, debug=debug, y16=y16,
+                          head_pad=pad)
         rgbs, _ = _DecoderFunction.apply(cfg, affine, as_nchw_view(x), *weights)
         data_dict['fake_rgbs'] = rgbs

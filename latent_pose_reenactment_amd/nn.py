@@ -526,23 +526,90 @@ G_F16_TAIL_DEFAULT = 0      # decoder blocks (from the output end) that run fp16
 RAW16_SKIP = os.environ.get('LP_G_RAW16', '1') != '0'      # conv2's epilogue also writes the raw planes of the block output for the next skip conv (0: a pack launch)
 
 
+class DecoderBlock(NamedTuple):
+    """one AdaIN residual block: where its tensors sit in ``_DecoderFunction``'s weight list and its AdaIN parameters in the affine row"""
+    cin: int
+    cout: int
+    up: bool
+    has_skip: bool                # a 1x1 skip conv with bias (cin != cout, or an up block); without one the block input itself is added
+    hout: int                     # side of the output map
+    phase: bool                   # conv1 runs in its phase-decomposed forms (``phase_conv``)
+    w1: int                       # weight-list indices: conv1, conv2, skip conv and its bias (None without a skip conv)
+    w2: int
+    ws: Optional[int]
+    bs: Optional[int]
+    o0: int                       # first affine column of AdaIN 0 (2 * cin columns: biases, then weights) and of AdaIN 1 (2 * cout)
+    o1: int
+    next_has_skip: bool           # the next block has a skip conv: what RAW16_SKIP lets conv2's epilogue write operand planes for
+
+
+class DecoderLayout(NamedTuple):
+    """Where everything sits in the decoder's flat interface (``decoder_layout``): the ``*weights`` list -- per block w1, w2[, w_skip, b_skip], then
+    w_head, b_head -- and the columns of the affine row, in consumption order.  Plain numbers: no tensors, no device state, no operand modes."""
+    blocks: Tuple[DecoderBlock, ...]
+    reflect: bool
+    wh: int                       # head conv: weight and bias indices, first affine column, input channels
+    bh: int
+    oh: int
+    ch: int
+    n_weights: int
+    n_affine: int
+    conv_idx: Tuple[int, ...]     # the entries that are conv weights (the others are biases), ascending = the order of ``_sn_layers``' decoder part
+    phase_idx: frozenset          # the w1 entries with ``phase``: weight-pack modes 2 / 3 instead of 0 / 1
+    block_of: Tuple[int, ...]     # per entry: the block that owns it; len(blocks) for the head's two
+
+
+def decoder_layout(blocks, in_size: int, reflect: bool) -> DecoderLayout:
+    """layout of a decoder of ``blocks`` = [(cin, cout, upsample)] on an ``in_size`` x ``in_size`` input map"""
+    skips = [cin != cout or bool(up) for cin, cout, up in blocks]
+    out, wi, off, size = [], 0, 0, in_size
+    for i, (cin, cout, up) in enumerate(blocks):
+        size *= 2 if up else 1
+        out.append(DecoderBlock(cin=cin, cout=cout, up=bool(up), has_skip=skips[i], hout=size, phase=phase_conv(up, size, reflect), w1=wi, w2=wi + 1,
+                                ws=wi + 2 if skips[i] else None, bs=wi + 3 if skips[i] else None, o0=off, o1=off + 2 * cin,
+                                next_has_skip=i + 1 < len(blocks) and skips[i + 1]))
+        wi += 4 if skips[i] else 2
+        off += 2 * (cin + cout)
+    ch = blocks[-1][1]
+    return DecoderLayout(blocks=tuple(out), reflect=bool(reflect), wh=wi, bh=wi + 1, oh=off, ch=ch, n_weights=wi + 2, n_affine=off + 2 * ch,
+                         conv_idx=tuple(i for b in out for i in (b.w1, b.w2, b.ws) if i is not None) + (wi,),
+                         phase_idx=frozenset(b.w1 for b in out if b.phase),
+                         block_of=tuple(i for i, b in enumerate(out) for _ in range(4 if b.has_skip else 2)) + (len(out),) * 2)
+
+
+class DecoderArgs(NamedTuple):
+    """the non-tensor argument of ``_DecoderFunction``"""
+    layout: DecoderLayout
+    prec: int                     # operand mode of the head conv (and the base mode of the pass)
+    precs: list                   # operand mode per block
+    need_grad: bool
+    sn: list                      # per weight-list entry: (u_used, v_used, [sigma, 1/sigma]) from SNBatch for conv weights, None for biases
+    packs: Optional[list]         # forward packs per entry prepared by the module (inference: cached; training: one batched launch), else packed on demand
+    packsT: Optional[list]        # data-gradient packs from the same batched launch (training), else packed on demand
+    debug: Optional[dict]         # when a dict: receives relu_planes / dz / dA_head / dx{i} / dh1_{i} / dxskip{i} (tie-masked parity checks)
+    y16: bool                     # 16-bit-resident conv outputs wanted (fp16 mode, zero padding)
+    head_pad: Optional[tuple] = None      # (w4, b4): the tanh head of generators/FSTH.py, see ``_DecoderFunction``
+
+
+def _inv_sigma(sn, i):
+    """the ``1/sigma`` device scalar of conv weight i: the ``alpha`` of its launches' epilogues"""
+    return sn[i][2][1:]
+
+
 class _DecoderFunction(torch.autograd.Function):
     """inputs: affine [B, n_aff] (projector output; per AdaIN: C biases then C weights, noBottleneck.py:108-125),
     constant [1,C,s,s] -- or a per-sample input [B,C,s,s] (the encoder output of generators/FSTH.py: its gradient comes back un-summed) --,
     then per block (w1, w2[, w_skip, b_skip]) and (w_head, b_head) -- the W_ORIG parameters themselves: 1/sigma of each
-    conv (``cfg['sn']``, from SNBatch) is the ``alpha`` of its launch's epilogue, W/sigma is never formed, and the weight-gradient launches
-    return the gradient w.r.t. W_orig through the legacy-hook rule (``snw``).
+    conv (``cfg.sn``, from SNBatch) is the ``alpha`` of its launch's epilogue, W/sigma is never formed, and the weight-gradient launches
+    return the gradient w.r.t. W_orig through the legacy-hook rule (``snw``).  ``cfg`` (DecoderArgs) carries the DecoderLayout both passes walk.
     outputs: fake_rgbs [B,3,S,S], fake_segm [B,1,S,S] (NCHW, noBottleneck.py:170-181).
-    ``cfg['head_pad']`` = (w4, b4): the head is the plain tanh of generators/FSTH.py -- a 3-row conv (w_head [3,C,3,3]) launched zero-padded to the 4
+    ``cfg.head_pad`` = (w4, b4): the head is the plain tanh of generators/FSTH.py -- a 3-row conv (w_head [3,C,3,3]) launched zero-padded to the 4
     rows the head kernels are built for (w4 / b4 hold the padded copies), fake_rgbs = tanh(z[..., :3]) (lp_tanh_head_*), fake_segm None."""
 
     @staticmethod
     def forward(ctx, cfg, affine, constant, *weights):
-        blocks, prec = cfg['blocks'], cfg['prec']
-        precs = cfg.get('precs') or [prec] * len(blocks)      # operand mode per block (``prec``: the head conv's and the default)
-        need_grad = cfg['need_grad']
-        sn = cfg['sn']                    # per entry of `weights`: (u_used, v_used, [sigma, 1/sigma]) for conv weights, None for biases
-        packs = cfg.get('packs')          # forward packs prepared by the module (inference: cached; training: one batched launch)
+        L, prec, precs, need_grad, sn, packs = cfg.layout, cfg.prec, cfg.precs, cfg.need_grad, cfg.sn, cfg.packs
+        reflect = L.reflect
 
         def fpack(i, w, phase=False, prec=prec):
             return packs[i] if packs is not None else ops.pack_weights(w.detach().contiguous(), 2 if phase else 0, prec)
@@ -550,16 +617,11 @@ class _DecoderFunction(torch.autograd.Function):
         affine = affine.contiguous()
         wl = list(weights)
         x = constant.detach().permute(0, 2, 3, 1).expand(B, -1, -1, -1).contiguous()    # NHWC
+        assert len(wl) == L.n_weights and affine.shape[1] == L.n_affine and x.shape[1] * (2 if L.blocks[0].up else 1) == L.blocks[0].hout
         saved = []
-        off = 0
-        wi = 0
 
-        def aff(c):
-            nonlocal off
-            beta, gamma = affine[:, off:off + c], affine[:, off + c:off + 2 * c]
-            o = off
-            off += 2 * c
-            return gamma, beta, o
+        def aff(o, c):          # (gamma, beta) of the AdaIN whose parameters start at column o
+            return affine[:, o + c:o + 2 * c], affine[:, o:o + c]
 
         # 16-BIT-RESIDENT conv outputs (round 5, fp16 mode, maps of >= 64 x 64 -- Y16_MIN_MAP; the conv epilogue also leaves the norm statistics there): a
         # conv between two AdaIN blocks writes the UNSCALED fp16 plane of y (+ the {count, mean, M2} partials from its fp32 accumulators) and no
@@ -569,8 +631,7 @@ class _DecoderFunction(torch.autograd.Function):
         # gen_padding='reflection' (noBottleneck.py:53-58: nn.ReflectionPad2d(1) in front of the ResBlocks' 3x3 convs, blocks.py:76-88; the head conv
         # keeps its zero padding, noBottleneck.py:80-88): the zero-padded conv + the border correction of csrc/reflect_border.hip; the statistics of a
         # conv output are then taken after the correction (no epilogue partials, no 16-bit-resident outputs)
-        reflect = bool(cfg.get('reflect'))
-        y16 = bool(cfg.get('y16')) and prec == PREC_F16 and all(p_ == PREC_F16 for p_ in precs) and not reflect
+        y16 = bool(cfg.y16) and prec == PREC_F16 and all(p_ == PREC_F16 for p_ in precs) and not reflect
 
         def dims(t):
             return tuple(t.hi.shape) if isinstance(t, ops.Act16) else tuple(t.shape)
@@ -602,56 +663,45 @@ class _DecoderFunction(torch.autograd.Function):
                 return y, cs, o16
             return ops.conv16(a, pk, prec=prec, stats=True, **kw) + (None,)
         x_cs = x_raw16 = None
-        for bi_, (cin, cout, up) in enumerate(blocks):
-            pb = precs[bi_]
-            w1, w2 = wl[wi], wl[wi + 1]
-            wi += 2
-            has_skip = (cin != cout) or up
-            g0, b0, o0 = aff(cin)
-            g1, b1, o1 = aff(cout)
-            hout = dims(x)[1] * (2 if up else 1)
+        for bi, b in enumerate(L.blocks):
+            pb, cin, cout, up, hout = precs[bi], b.cin, b.cout, b.up, b.hout
+            w1, w2 = wl[b.w1], wl[b.w2]
+            g0, b0 = aff(b.o0, cin)
+            g1, b1 = aff(b.o1, cout)
             # AdaIN + ReLU are applied ONCE per tensor while it is packed to the conv's 16-bit operand planes (the same planes feed
             # the weight gradient in backward); the convs themselves stage their operands by LDS-DMA only
             st0 = in_stats(x, x_cs, g0, b0)
             a0 = norm_planes(x, st0, pb)
-            ph1 = phase_conv(up, hout, reflect)
-            p1 = fpack(wi - 2, w1, ph1, pb)
-            h1, cs1, _ = conv_out(a0, p1, hout, w1, pb, ksize=3, upsample=up, alpha=sn[wi - 2][2][1:], **({'phase': True} if ph1 else {}))
+            p1 = fpack(b.w1, w1, b.phase, pb)
+            h1, cs1, _ = conv_out(a0, p1, hout, w1, pb, ksize=3, upsample=up, alpha=_inv_sigma(sn, b.w1), **({'phase': True} if b.phase else {}))
             st1 = in_stats(h1, cs1, g1, b1)
             a1 = norm_planes(h1, st1, pb)
             xs = None
-            if has_skip:
-                ws, bs = wl[wi], wl[wi + 1]
-                wi += 2
-                ps = fpack(wi - 2, ws, False, pb)
+            if b.has_skip:
+                ps = fpack(b.ws, wl[b.ws], False, pb)
                 xs = x if isinstance(x, ops.Act16) else x_raw16 if x_raw16 is not None else ops.act_pack(x, pro=0, prec=pb)
-                s = ops.conv16(xs, ps, ksize=1, bias=bs.detach().contiguous(), alpha=sn[wi - 2][2][1:], prec=pb)   # 1x1 commutes with nearest upsampling
+                s = ops.conv16(xs, ps, ksize=1, bias=wl[b.bs].detach().contiguous(), alpha=_inv_sigma(sn, b.ws), prec=pb)   # 1x1 commutes with nearest upsampling
                 rs = 1 if up else 0
             else:
                 assert not isinstance(x, ops.Act16), 'an identity skip adds the fp32 block input (blocks without a skip conv sit on the smallest maps)'
                 s, rs = x, 0
-            i2 = wi - (3 if has_skip else 1)
-            p2 = fpack(i2, w2, False, pb)
-            nxt = blocks[bi_ + 1] if bi_ + 1 < len(blocks) else None
-            out, x_cs, x_raw16 = conv_out(a1, p2, hout, w2, pb, raw16=RAW16_SKIP and nxt is not None and (nxt[0] != nxt[1] or nxt[2]) and precs[bi_ + 1] == pb,
-                                          ksize=3, res=s, res_shift=rs, alpha=sn[i2][2][1:])
+            p2 = fpack(b.w2, w2, False, pb)
+            out, x_cs, x_raw16 = conv_out(a1, p2, hout, w2, pb, raw16=RAW16_SKIP and b.next_has_skip and precs[bi + 1] == pb,
+                                          ksize=3, res=s, res_shift=rs, alpha=_inv_sigma(sn, b.w2))
             if need_grad:
-                saved.append((x, h1, st0, st1, o0, o1, a0, a1, xs))
-            if cfg.get('debug') is not None:      # activation patterns of the AdaIN+ReLU sites (tie-masked parity checks)
-                cfg['debug'].setdefault('relu_planes', []).extend([a0.hi, a1.hi])
+                saved.append((x, h1, st0, st1, a0, a1, xs))
+            if cfg.debug is not None:      # activation patterns of the AdaIN+ReLU sites (tie-masked parity checks)
+                cfg.debug.setdefault('relu_planes', []).extend([a0.hi, a1.hi])
             x = out
-        ch = blocks[-1][1]
-        gh, bh, oh = aff(ch)
+        gh, bh = aff(L.oh, L.ch)
         sth = in_stats(x, x_cs, gh, bh)
-        wh, bhd = wl[wi], wl[wi + 1]
-        head_pad = cfg.get('head_pad')
-        if head_pad is not None:
-            wh, bhd = head_pad
-        ph = fpack(wi, wh)
+        head_pad = cfg.head_pad
+        wh, bhd = (wl[L.wh], wl[L.bh]) if head_pad is None else head_pad
+        ph = fpack(L.wh, wh)
         ah = norm_planes(x, sth)
-        z = ops.conv16(ah, ph, ksize=3, bias=bhd.detach().contiguous(), alpha=sn[wi][2][1:], prec=prec)
-        if cfg.get('debug') is not None:
-            cfg['debug'].setdefault('relu_planes', []).append(ah.hi)
+        z = ops.conv16(ah, ph, ksize=3, bias=bhd.detach().contiguous(), alpha=_inv_sigma(sn, L.wh), prec=prec)
+        if cfg.debug is not None:
+            cfg.debug.setdefault('relu_planes', []).append(ah.hi)
         if head_pad is not None:
             (t, rgbs), segm = ops.tanh_head_fwd(z, want_t=need_grad), None
         else:
@@ -659,7 +709,7 @@ class _DecoderFunction(torch.autograd.Function):
         if need_grad:
             ctx.cfg = cfg
             ctx.saved = saved
-            ctx.head = (x, sth, oh, t, ah)
+            ctx.head = (x, sth, t, ah)
             ctx.affine = affine
             ctx.weights = [w.detach() for w in wl]
             ctx.params = wl                  # the parameter tensors themselves: fused accumulation adds into their .grad
@@ -669,11 +719,9 @@ class _DecoderFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_rgbs, d_segm):
         cfg = ctx.cfg
-        blocks, prec = cfg['blocks'], cfg['prec']
-        precs = cfg.get('precs') or [prec] * len(blocks)      # operand mode per block; ``prec``: the head conv
+        L, prec, precs, sn = cfg.layout, cfg.prec, cfg.precs, cfg.sn      # ``precs``: operand mode per block; ``prec``: the head conv
         f16 = prec == PREC_F16          # gradient tensors become fp16 operands: their producers fold max|.| in (no amax pass)
-        sn = cfg['sn']
-        reflect = bool(cfg.get('reflect'))
+        reflect = L.reflect
         affine, wl = ctx.affine, ctx.weights
         params = ctx.params
         d_affine = torch.zeros_like(affine)
@@ -684,7 +732,7 @@ class _DecoderFunction(torch.autograd.Function):
             corr = ops.reflect_border_wgrad(a, dy, prec=prec, upsample=up, sn=snw(i), accum=_accum_target(params[i]))
             if corr is not None:
                 grads[i] = grads[i] + corr
-            ops.reflect_border_dgrad(dy, wl[i].contiguous(), sn[i][2][1:], dA)
+            ops.reflect_border_dgrad(dy, wl[i].contiguous(), _inv_sigma(sn, i), dA)
 
         def snw(i):          # (W_orig, u, v, sig) of conv weight i -> wgrad returns the gradient w.r.t. W_orig
             return (wl[i],) + tuple(sn[i])
@@ -693,96 +741,89 @@ class _DecoderFunction(torch.autograd.Function):
         def slices(o, c):      # (gamma, dgamma, dbeta) views for the AdaIN whose params start at column o
             return affine[:, o + c:o + 2 * c], d_affine[:, o + c:o + 2 * c], d_affine[:, o:o + c]
 
-        x, sth, oh, t, ah = ctx.head
-        ch = blocks[-1][1]
-        head_pad = cfg.get('head_pad')
+        x, sth, t, ah = ctx.head
+        wh, ch, head_pad = L.wh, L.ch, cfg.head_pad
         if head_pad is not None:
             dz = ops.tanh_head_bwd(t, d_rgbs.contiguous(), amax=f16)
         else:
             dz = ops.head_bwd(t, d_rgbs.contiguous(), None if d_segm is None else d_segm.contiguous(), amax=f16)
-        wi = len(wl) - 2
         # (tanh head: the launch is the padded 4-row one; the raw gradient's rows 0..2 then take the spectral-norm rule of the [3, C, 3, 3] parameter)
-        hsn, haccum = (None, None) if head_pad is not None else (snw(wi), _accum_target(params[wi]))
+        hsn, haccum = (None, None) if head_pad is not None else (snw(wh), _accum_target(params[wh]))
         if ops.thin_wgrad_supported(ch, dz.shape[3], 3, 1, dz.shape[2]):
             thin = ops.thin_wgrad16 if isinstance(x, ops.Act16) else ops.thin_wgrad
-            grads[wi], grads[wi + 1] = thin(x, dz, ksize=3, pro=1, scale=sth[2], shift=sth[3], sn=hsn, accum=haccum, bias_grad=True)
+            grads[wh], grads[L.bh] = thin(x, dz, ksize=3, pro=1, scale=sth[2], shift=sth[3], sn=hsn, accum=haccum, bias_grad=True)
         else:
-            grads[wi], grads[wi + 1] = ops.conv_wgrad16(ah, ops.act_pack(dz, prec=prec, grad=True), ksize=3, prec=prec, sn=hsn, accum=haccum, bias_grad=True)
+            grads[wh], grads[L.bh] = ops.conv_wgrad16(ah, ops.act_pack(dz, prec=prec, grad=True), ksize=3, prec=prec, sn=hsn, accum=haccum, bias_grad=True)
         if head_pad is not None:
-            rows = wl[wi].shape[0]
-            grads[wi] = ops.sn_grad_apply(grads[wi][:rows].contiguous(), wl[wi].contiguous(), *sn[wi], accum=_accum_target(params[wi]))
-            grads[wi + 1] = grads[wi + 1][:rows].contiguous()
-        packsT = cfg.get('packsT')        # dgrad packs from the same batched launch (training), else packed on demand
+            rows = wl[wh].shape[0]
+            grads[wh] = ops.sn_grad_apply(grads[wh][:rows].contiguous(), wl[wh].contiguous(), *sn[wh], accum=_accum_target(params[wh]))
+            grads[L.bh] = grads[L.bh][:rows].contiguous()
+        packsT = cfg.packsT
 
-        def tpack(i, small_k=False, phase=False, prec=prec):
+        def tpack(i, small_k=False, phase=False, prec=prec, src=None):
             if packsT is not None:
                 return packsT[i]
-            src = head_pad[0] if (head_pad is not None and i == len(wl) - 2) else wl[i]
-            return ops.pack_weights(src.contiguous(), 3 if phase else 1, prec, small_k=small_k)
-        pT = tpack(wi, small_k=True)
-        dA = ops.conv(dz, pT, ksize=3, alpha=sn[wi][2][1:], prec=prec, grad=True)
-        g, dg, db = slices(oh, ch)
+            return ops.pack_weights((wl[i] if src is None else src).contiguous(), 3 if phase else 1, prec, small_k=small_k)
+        pT = tpack(wh, small_k=True, src=None if head_pad is None else head_pad[0])
+        dA = ops.conv(dz, pT, ksize=3, alpha=_inv_sigma(sn, wh), prec=prec, grad=True)
+        g, dg, db = slices(L.oh, ch)
         # bf16 / bf16x3 (round 6): gradient operands carry no scale there, so the AdaIN backward (and the 2x2 sum of the skip branch) write the
         # operand planes of their result themselves -- lp_adain_relu_bwd_planes / lp_sum2x2_planes: no pack launch, and the conv1-output gradient
         # (dh1), whose only consumers are the two contractions, never exists in fp32
         # A gradient's operand planes are written in the mode of the block that CONSUMES them (``precs``: the blocks of one decoder may differ).
         def is_direct(p_):
             return p_ in (PREC_BF16, PREC_BF16X3)
-        dbg = cfg.get('debug')
+        dbg = cfg.debug
         dx16 = None
         if is_direct(precs[-1]):
             dx, dx16 = ops.adain_relu_bwd(dA, x, None, g, sth[0], sth[1], sth[2], sth[3], dg, db, False, planes=precs[-1])
         else:
             dx = ops.adain_relu_bwd(dA, x, None, g, sth[0], sth[1], sth[2], sth[3], dg, db, False, amax=precs[-1] == PREC_F16)
         if dbg is not None:
-            dbg['dz'] = dz; dbg['dA_head'] = dA; dbg[f'dx{len(blocks)}'] = dx
+            dbg['dz'] = dz; dbg['dA_head'] = dA; dbg[f'dx{len(L.blocks)}'] = dx
 
-        for bi in range(len(blocks) - 1, -1, -1):
-            cin, cout, up = blocks[bi]
-            has_skip = (cin != cout) or up
-            x, h1, st0, st1, o0, o1, a0, a1, xs = ctx.saved[bi]
-            wi -= 4 if has_skip else 2
+        for bi, b in reversed(list(enumerate(L.blocks))):
+            cin, cout, up = b.cin, b.cout, b.up
+            x, h1, st0, st1, a0, a1, xs = ctx.saved[bi]
             prec = precs[bi]                 # this block's operand mode; the gradient it hands on is packed for block bi - 1
             pnext = precs[bi - 1] if bi > 0 else prec
             direct, f16 = is_direct(prec), prec == PREC_F16
             d_out = dx
             d16 = dx16 if dx16 is not None else ops.act_pack(d_out, prec=prec, grad=True)       # packed once: operand of conv2's weight AND data gradient
             # conv2 (+ AdaIN1/ReLU prologue)
-            grads[wi + 1] = ops.conv_wgrad16(a1, d16, ksize=3, prec=prec, sn=snw(wi + 1), accum=_accum_target(params[wi + 1]))
-            dA1 = ops.conv16(d16, tpack(wi + 1, prec=prec), ksize=3, alpha=sn[wi + 1][2][1:], prec=prec)
+            grads[b.w2] = ops.conv_wgrad16(a1, d16, ksize=3, prec=prec, sn=snw(b.w2), accum=_accum_target(params[b.w2]))
+            dA1 = ops.conv16(d16, tpack(b.w2, prec=prec), ksize=3, alpha=_inv_sigma(sn, b.w2), prec=prec)
             if reflect:
-                border(wi + 1, a1, d_out, dA1, prec=prec)
-            g, dg, db = slices(o1, cout)
+                border(b.w2, a1, d_out, dA1, prec=prec)
+            g, dg, db = slices(b.o1, cout)
             if direct:
                 dh1, dh16 = ops.adain_relu_bwd(dA1, h1, None, g, st1[0], st1[1], st1[2], st1[3], dg, db, False, planes=prec, keep_dx=reflect or dbg is not None)
             else:
                 dh1 = ops.adain_relu_bwd(dA1, h1, None, g, st1[0], st1[1], st1[2], st1[3], dg, db, False, amax=f16)
                 dh16 = None
             # skip branch: out += up2(conv1x1(x) + b)
-            if has_skip:
+            if b.has_skip:
                 if up:
                     ds16 = ops.sum2x2_planes(d_out, prec) if direct else ops.act_pack(ops.sum2x2(d_out, amax=f16), prec=prec, grad=True)
                 else:
                     ds16 = d16
-                grads[wi + 2], grads[wi + 3] = ops.conv_wgrad16(xs, ds16, ksize=1, prec=prec, sn=snw(wi + 2),
-                                                                accum=_accum_target(params[wi + 2]), bias_grad=True,
-                                                                bias_accum=_accum_target(params[wi + 3]))
-                dx_skip = ops.conv16(ds16, tpack(wi + 2, prec=prec), ksize=1, alpha=sn[wi + 2][2][1:], prec=prec)
+                grads[b.ws], grads[b.bs] = ops.conv_wgrad16(xs, ds16, ksize=1, prec=prec, sn=snw(b.ws), accum=_accum_target(params[b.ws]),
+                                                            bias_grad=True, bias_accum=_accum_target(params[b.bs]))
+                dx_skip = ops.conv16(ds16, tpack(b.ws, prec=prec), ksize=1, alpha=_inv_sigma(sn, b.ws), prec=prec)
             else:
                 dx_skip = d_out
             # conv1 (+ AdaIN0/ReLU/upsample prologue)
             if dh16 is None:
                 dh16 = ops.act_pack(dh1, prec=prec, grad=True)
-            grads[wi] = ops.conv_wgrad16(a0, dh16, ksize=3, upsample=up, prec=prec, sn=snw(wi), accum=_accum_target(params[wi]))
-            ph1 = phase_conv(up, dh16.hi.shape[1], reflect)
-            if ph1:      # phase form of the data gradient: the gradient w.r.t. the LOW-resolution AdaIN output from one launch (2 x 2 sum included)
-                dA0 = ops.conv16(dh16, tpack(wi, phase=True, prec=prec), ksize=3, alpha=sn[wi][2][1:], prec=prec, phase_dgrad=True)
+            grads[b.w1] = ops.conv_wgrad16(a0, dh16, ksize=3, upsample=up, prec=prec, sn=snw(b.w1), accum=_accum_target(params[b.w1]))
+            if b.phase:      # phase form of the data gradient: the gradient w.r.t. the LOW-resolution AdaIN output from one launch (2 x 2 sum included)
+                dA0 = ops.conv16(dh16, tpack(b.w1, phase=True, prec=prec), ksize=3, alpha=_inv_sigma(sn, b.w1), prec=prec, phase_dgrad=True)
             else:
-                dA0 = ops.conv16(dh16, tpack(wi, prec=prec), ksize=3, alpha=sn[wi][2][1:], prec=prec)
+                dA0 = ops.conv16(dh16, tpack(b.w1, prec=prec), ksize=3, alpha=_inv_sigma(sn, b.w1), prec=prec)
             if reflect:
-                border(wi, a0, dh1, dA0, up, prec=prec)
-            up_bwd = up and not ph1          # (the fused-upsample form hands the AdaIN backward a 2H x 2W gradient to sum)
-            g, dg, db = slices(o0, cin)
+                border(b.w1, a0, dh1, dA0, up, prec=prec)
+            up_bwd = up and not b.phase          # (the fused-upsample form hands the AdaIN backward a 2H x 2W gradient to sum)
+            g, dg, db = slices(b.o0, cin)
             dx16 = None
             if is_direct(pnext) and bi > 0:          # (block 0's input gradient only feeds the learned constant: fp32)
                 dx, dx16 = ops.adain_relu_bwd(dA0, x, dx_skip, g, st0[0], st0[1], st0[2], st0[3], dg, db, up_bwd, planes=pnext)
@@ -832,7 +873,7 @@ class Generator(nn.Module):
         self.identity_embedding_size = identity_embedding_size
         self.pose_embedding_size = pose_embedding_size
         joint = identity_embedding_size + pose_embedding_size
-        self.num_affine_params = sum(2 * (a + b) for a, b, _ in self.blocks_cfg) + 2 * self.blocks_cfg[-1][1]
+        self.num_affine_params = self._layout().n_affine
         self.affine_params_projector = self._build_projector(joint)
         self.finetuning = False
         self.prec = generator_prec() if prec is None else prec
@@ -850,12 +891,19 @@ class Generator(nn.Module):
         k = min(self.f16_tail, nb) if prec == PREC_BF16X3 else 0
         return [prec] * (nb - k) + [PREC_F16] * k
 
-    def _weight_precs(self, precs, prec):
-        """operand mode per entry of ``_conv_weights``' list (biases: their conv's), the head conv in the base mode"""
-        out = []
-        for (cin, cout, up), p_ in zip(self.blocks_cfg, precs):
-            out += [p_] * (4 if (cin != cout or up) else 2)
-        return out + [prec, prec]
+    # ---- where the decoder's modules differ between the plugins: the head conv's place and where the input map comes from
+    def _head(self):
+        return self.decoder_blocks._modules[str(len(self.blocks_cfg) + 2)]
+
+    def _decoder_in_size(self):
+        return self.constant.constant.shape[-1]
+
+    def _layout(self) -> DecoderLayout:
+        key = (self._decoder_in_size(), self.reflect)
+        cache = self.__dict__.setdefault('_layouts', {})
+        if key not in cache:
+            cache[key] = decoder_layout(self.blocks_cfg, *key)
+        return cache[key]
 
     # ---- the projector is the only part in which the generator plugins differ (noBottleneck.py:96-101 vs FSTH_plus.py:96-103)
     def _build_projector(self, joint):
@@ -914,54 +962,61 @@ class Generator(nn.Module):
             self.__dict__['_sn_batch'] = SNBatch(layers)
         return self._sn_batch.update(self.training)
 
+    def _decoder_sn_layers(self):
+        """the decoder's SNWeight modules in the order of ``DecoderLayout.conv_idx``: per block w1, w2[, skip], then the head conv"""
+        mods = self.decoder_blocks._modules
+        return [c for i in range(len(self.blocks_cfg)) for c in mods[str(i)].convs() if c is not None] + [self._head()]
+
     def _conv_weights(self, states):
-        """(weights, sn): the decoder's conv weights / biases in _DecoderFunction's argument order, with each conv's SN state"""
-        weights, sn = [], []
-        nb = len(self.blocks_cfg)
-        k = 0
-        for i in range(nb):
-            c1, c2, sk = self.decoder_blocks._modules[str(i)].convs()
-            weights += [c1.weight_orig, c2.weight_orig]
-            sn += [states[k], states[k + 1]]
-            k += 2
-            if sk is not None:
-                weights += [sk.weight_orig, sk.bias]
-                sn += [states[k], None]
-                k += 1
-        head = self.decoder_blocks._modules[str(nb + 2)]
-        weights += [head.weight_orig, head.bias]
-        sn += [states[k], None]
+        """(weights, sn): the decoder's conv weights / biases in _DecoderFunction's argument order, with each conv's SN state (``states``: of
+        ``_sn_layers``, which starts with the decoder's convs)"""
+        L = self._layout()
+        weights, sn = [None] * L.n_weights, [None] * L.n_weights
+        for i, conv, st in zip(L.conv_idx, self._sn_layers()[0], states):          # (entry k of ``states`` belongs to layer k)
+            weights[i], sn[i] = conv.weight_orig, st
+        for b, blk in zip(L.blocks, self.decoder_blocks._modules.values()):
+            if b.has_skip:
+                weights[b.bs] = blk.convs()[2].bias
+        weights[L.bh] = self._head().bias
         return weights, sn
 
-    def _train_packs_update(self, weights, sn):
-        """training: every conv weight changed in the last optimizer step -> ONE launch re-packs all of them, both orientations"""
-        conv_idx = [i for i, s_ in enumerate(sn) if s_ is not None]
-        ph = self._phase_weight_indices()          # conv1 of the up blocks that run in their phase forms: pack modes 2 / 3 instead of 0 / 1
-        specs = [(weights[i], 2 if i in ph else 0, False) for i in conv_idx] + [(weights[i], 3 if i in ph else 1, i == len(weights) - 2) for i in conv_idx]
-        wp = self._weight_precs(self.block_precs(self.prec), self.prec)
-        sp = tuple(wp[i] for i in conv_idx) * 2
+    def _train_packs_update(self, src):
+        """training: every conv weight changed in the last optimizer step -> ONE launch re-packs all of them (``src``: the weight list), both orientations"""
+        L = self._layout()
+        ci, ph = L.conv_idx, L.phase_idx          # conv1 of the up blocks that run in their phase forms: pack modes 2 / 3 instead of 0 / 1
+        specs = [(src[i], 2 if i in ph else 0, False) for i in ci] + [(src[i], 3 if i in ph else 1, i == L.wh) for i in ci]
+        modes = self.block_precs(self.prec) + [self.prec]
+        sp = tuple(modes[L.block_of[i]] for i in ci) * 2
         pb = self.__dict__.get('_train_packs')
         if pb is None or pb.prec != self.prec or pb.precs != sp or pb.key != tuple((w.data_ptr(), m, bool(k_)) for w, m, k_ in specs):
             pb = ops.PackBatch(specs, self.prec, sp)
             self.__dict__['_train_packs'] = pb
         allp = pb.update()
-        packs, packsT = [None] * len(weights), [None] * len(weights)
-        for j, i in enumerate(conv_idx):
-            packs[i], packsT[i] = allp[j], allp[len(conv_idx) + j]
+        packs, packsT = [None] * L.n_weights, [None] * L.n_weights
+        for j, i in enumerate(ci):
+            packs[i], packsT[i] = allp[j], allp[len(ci) + j]
         return packs, packsT
 
-    def _phase_weight_indices(self):
-        """indices (into ``_conv_weights``' list) of the conv1 weights whose up block runs the phase-decomposed forms (``phase_conv``)"""
-        cached = self.__dict__.get('_phase_idx')
-        if cached is None:
-            cached, wi, size = set(), 0, self.constant.constant.shape[-1]
-            for cin, cout, up in self.blocks_cfg:
-                size *= 2 if up else 1
-                if phase_conv(up, size, self.reflect):
-                    cached.add(wi)
-                wi += 4 if (cin != cout or up) else 2
-            self.__dict__['_phase_idx'] = cached
-        return cached
+    def _decoder_packs(self, weights, src, prec, precs, need_grad, prepared=None):
+        """(packs, packsT) per weight-list entry for ``_DecoderFunction``; ``src``: the tensors to pack (``weights``, or with a padded head).  Training: the
+        batched re-pack (``prepared``: ``prepare_step`` already ran it); inference: cached forward packs; any other pass packs on demand (None)."""
+        if need_grad and self.training:
+            return prepared if prepared is not None else self._train_packs_update(src)
+        if need_grad or self.training:
+            return None, None
+        # inference (drive.py): the weights do not change between frames -> pack them to 16 bit once.  The key also carries the generation counter of
+        # the fused optimizer / EMA kernels: those update weights through raw pointers without bumping ``_version`` (a graph replay bumps neither:
+        # GraphedTrainStep.__call__ advances the counter itself).
+        from .optim import WEIGHTS_GENERATION
+        L = self._layout()
+        key = (prec, tuple(precs), self._decoder_in_size(), WEIGHTS_GENERATION[0]) + tuple((w.data_ptr(), w._version) for w in weights)
+        cache = self.__dict__.get('_pack_cache')
+        if cache is None or cache[0] != key:
+            packs, modes = [None] * L.n_weights, list(precs) + [prec]
+            for i in L.conv_idx:
+                packs[i] = ops.pack_weights(src[i].detach().contiguous(), 2 if i in L.phase_idx else 0, modes[L.block_of[i]])
+            cache = self.__dict__['_pack_cache'] = (key, packs)
+        return cache[1], None
 
     def prepare_step(self):
         """The parts of a TRAINING forward that depend on the weights only -- the spectral-norm power iteration and the 16-bit weight packs
@@ -971,54 +1026,26 @@ class Generator(nn.Module):
             return
         states = self._sn_update()
         self.__dict__['_prepared_sn'] = states
-        weights, sn = self._conv_weights(states)
+        weights, _ = self._conv_weights(states)
         if any(w.requires_grad for w in weights):
-            self.__dict__['_prepared_packs'] = self._train_packs_update(weights, sn)
+            self.__dict__['_prepared_packs'] = self._train_packs_update(weights)
 
     def _sn_layers(self):
         """batched SNWeight layers in a fixed order: decoder convs (block order, w1, w2[, skip]), head conv, projector.0, projector.2"""
         cached = self.__dict__.get('_sn_layer_cache')
         if cached is None:
-            layers = []
-            nb = len(self.blocks_cfg)
-            for i in range(nb):
-                c1, c2, sk = self.decoder_blocks._modules[str(i)].convs()
-                layers += [c1, c2] + ([sk] if sk is not None else [])
-            layers.append(self.decoder_blocks._modules[str(nb + 2)])
-            layers += self._projector_sn_layers()
-            cached = (layers, None)
-            self.__dict__['_sn_layer_cache'] = cached
+            cached = self.__dict__['_sn_layer_cache'] = (self._decoder_sn_layers() + self._projector_sn_layers(), None)
         return cached
 
     def forward(self, data_dict):
         affine = self._affine_params(data_dict)
-        states = self._sn_states
-        weights, sn = self._conv_weights(states)
+        weights, sn = self._conv_weights(self._sn_states)
         need_grad = torch.is_grad_enabled() and (affine.requires_grad or any(w.requires_grad for w in weights))
         prec = self.prec if need_grad else self.infer_prec
         precs = self.block_precs(prec)
-        packs = packsT = None
-        prepared = self.__dict__.pop('_prepared_packs', None)
-        if not torch.is_grad_enabled():
-            prepared = None
-        if need_grad and self.training:
-            packs, packsT = prepared if prepared is not None else self._train_packs_update(weights, sn)
-        if not need_grad and not self.training:
-            # inference (drive.py): the weights do not change between frames -> pack them to 16 bit once.  The key also carries the
-            # generation counter of the fused optimizer / EMA kernels: those update weights through raw pointers without bumping
-            # ``_version`` (a graph replay bumps neither: GraphedTrainStep.__call__ advances the counter itself).
-            from .optim import WEIGHTS_GENERATION
-            key = (prec, tuple(precs), WEIGHTS_GENERATION[0]) + tuple((w.data_ptr(), w._version) for w in weights)
-            cache = self.__dict__.get('_pack_cache')
-            if cache is None or cache[0] != key:
-                ph = self._phase_weight_indices()
-                wp = self._weight_precs(precs, prec)
-                cache = (key, [ops.pack_weights(w.detach().contiguous(), 2 if i in ph else 0, wp[i]) if s_ is not None else None
-                               for i, (w, s_) in enumerate(zip(weights, sn))])
-                self.__dict__['_pack_cache'] = cache
-            packs = cache[1]
-        cfg = dict(blocks=self.blocks_cfg, prec=prec, precs=precs, need_grad=need_grad, sn=sn, packs=packs, packsT=packsT,
-                   debug=getattr(self, '_debug', None), y16=G_Y16 and self.training and need_grad, reflect=self.reflect)
+        packs, packsT = self._decoder_packs(weights, weights, prec, precs, need_grad, self.__dict__.pop('_prepared_packs', None))
+        cfg = DecoderArgs(layout=self._layout(), prec=prec, precs=precs, need_grad=need_grad, sn=sn, packs=packs, packsT=packsT,
+                          debug=getattr(self, '_debug', None), y16=G_Y16 and self.training and need_grad)
         rgbs, segm = _DecoderFunction.apply(cfg, affine, self.constant.constant, *weights)
         data_dict['fake_rgbs'] = rgbs
         data_dict['fake_segm'] = segm
