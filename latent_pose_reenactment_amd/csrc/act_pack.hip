@@ -13,19 +13,6 @@
 // multiple of the group count G whenever G is a power of two, so its group -- and with it the AdaIN scale/shift of its 8 channels
 // -- is fixed and loaded once; 4 items are in flight per thread (8 x 16-B loads) to cover the HBM latency.
 #define AMAX_BLOCKS 1024
-// amax -> power-of-two input scale of an fp16 gradient operand: s = 2^(13 - e) with amax = f * 2^e, f in [0.5, 1): the scaled
-// tensor's amax lands in [2^12, 2^13) -- 3 binades of headroom below the fp16 maximum, 26 binades of normal range below
-__device__ __forceinline__ void amax_to_scale(float m, float& s, float& inv) {
-    s = 1.f; inv = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-        int e;
-        (void)frexpf(m, &e);
-        int k = 13 - e;
-        k = k > 100 ? 100 : (k < -100 ? -100 : k);
-        s = ldexpf(1.f, k); inv = ldexpf(1.f, -k);
-    }
-}
-
 template <int PREC>
 __global__ __launch_bounds__(256) void act_pack_kernel(const float* __restrict__ x, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, int pro, uint16_t* __restrict__ hi,

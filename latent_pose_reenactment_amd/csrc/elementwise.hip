@@ -1,5 +1,5 @@
-// HBM-bound helper kernels of the generator path (gfx950): weight packing, instance-norm statistics, AdaIN/ReLU
-// backward, 2x2 block sums, generator head.  All NHWC fp32, float4-vectorised, coalesced along channels.
+// HBM-bound helper kernels of the generator path (gfx950): weight packing, instance-norm statistics, 2x2 block sums,
+// generator head (the AdaIN/ReLU backward: norm_bwd.hip).  All NHWC fp32, float4-vectorised, coalesced along channels.
 #include "lp_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
@@ -343,224 +343,6 @@ extern "C" int lp_bn_train_stats(const float* y, const float* gamma, const float
     hipLaunchKernelGGL(instnorm_finalize_kernel<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, workspace, gamma, beta, C, eps, mean, rstd, scale, shift,
                        1, C, S, running_mean, running_var, momentum);
     return lp_check_launch("bn_stats_finalize");
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// backward of relu(AdaIN(x)) [+ x2 nearest upsample]
-//   pass 1: g = sum2x2?(dA) * mask  -> written into dx (as temporary), partial sums S1 = sum g, S2 = sum g*xhat
-//   pass 2: coefficients; pass 3: dx = ca*g + cb*x + cc (+ add)
-// ------------------------------------------------------------------------------------------------------------------
-// mask_mode 0: the activation's own pattern 0 < x*scale+shift < act_hi (ReLU: act_hi = inf; ReLU6: 6);  1: no mask (a plain norm);
-// 2: mask_src > 0 (the ReLU sits behind a residual add: mask_src = the block output).  g_copy (|NULL): the masked gradient g is also
-// written there (the identity branch of the residual block receives exactly that).
-// X16: x is a 16-BIT-RESIDENT conv output (the unscaled fp16 plane [N][HW][C] the conv epilogue left instead of fp32 y; C % 8 == 0)
-template <bool X16> __device__ __forceinline__ float4 lp_ldx4(const void* x, size_t e) {
-    if (X16) {
-        const ushort4 h = *(const ushort4*)((const uint16_t*)x + e);
-        return make_float4(lp_op16_to_f32<true>(h.x), lp_op16_to_f32<true>(h.y), lp_op16_to_f32<true>(h.z), lp_op16_to_f32<true>(h.w));
-    }
-    return *(const float4*)((const float*)x + e);
-}
-
-// four consecutive channels of a gradient tensor as bf16 operand planes: hi = RNE bf16, lo = bf16(v - hi) (|NULL: plain bf16 mode)
-__device__ __forceinline__ void lp_store_bf16_planes4(const float4& o, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, size_t e) {
-    const float v[4] = {o.x, o.y, o.z, o.w};
-    ushort4 h, l;
-    uint16_t* hp = (uint16_t*)&h; uint16_t* lp = (uint16_t*)&l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        hp[j] = lp_f32_to_op16<false>(v[j]);
-        lp[j] = lp_f32_to_op16<false>(v[j] - lp_op16_to_f32<false>(hp[j]));
-    }
-    *(ushort4*)(hi + e) = h;
-    if (lo) *(ushort4*)(lo + e) = l;
-}
-
-template <bool X16 = false>
-__global__ __launch_bounds__(256) void adain_bwd_partial_kernel(const float* __restrict__ dA, const void* __restrict__ x,
-                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                float* __restrict__ g_out, float* __restrict__ part, int H, int W, int C,
-                                                                int ups, int S, int PB, int mask_mode = 0, const float* __restrict__ mask_src = nullptr,
-                                                                float* __restrict__ g_copy = nullptr, float act_hi = 3.0e38f) {
-    __shared__ float sh[2][16][64];
-    const int n = blockIdx.z, cb = blockIdx.y, s = blockIdx.x;
-    const int cq = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int c = cb * 64 + cq * 4;
-    const int HW = H * W;
-    const int p0 = s * PB, p1 = min(HW, p0 + PB);
-    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    if (c < C) {                                       // C % 4 == 0 required (checked on host)
-        float4 mu = *(const float4*)(mean + (size_t)n * C + c), rs = *(const float4*)(rstd + (size_t)n * C + c);
-        float4 sc = *(const float4*)(scale + (size_t)n * C + c), sf = *(const float4*)(shift + (size_t)n * C + c);
-#pragma unroll 2
-        for (int pix = p0 + pl; pix < p1; pix += 16) {
-            float4 xv = lp_ldx4<X16>(x, ((size_t)n * HW + pix) * C + c);
-            float4 g;
-            if (ups) {
-                int yy = pix / W, xx = pix % W;
-                const float* b = dA + (((size_t)n * 2 * H + 2 * yy) * 2 * W + 2 * xx) * C + c;
-                float4 a0 = *(const float4*)b, a1 = *(const float4*)(b + C), a2 = *(const float4*)(b + (size_t)2 * W * C),
-                       a3 = *(const float4*)(b + (size_t)2 * W * C + C);
-                g.x = (a0.x + a1.x) + (a2.x + a3.x); g.y = (a0.y + a1.y) + (a2.y + a3.y);
-                g.z = (a0.z + a1.z) + (a2.z + a3.z); g.w = (a0.w + a1.w) + (a2.w + a3.w);
-            } else g = *(const float4*)(dA + ((size_t)n * HW + pix) * C + c);
-            if (mask_mode == 0) {
-                const float a0 = fmaf(xv.x, sc.x, sf.x), a1 = fmaf(xv.y, sc.y, sf.y), a2 = fmaf(xv.z, sc.z, sf.z), a3 = fmaf(xv.w, sc.w, sf.w);
-                g.x = (a0 > 0.f && a0 < act_hi) ? g.x : 0.f; g.y = (a1 > 0.f && a1 < act_hi) ? g.y : 0.f;
-                g.z = (a2 > 0.f && a2 < act_hi) ? g.z : 0.f; g.w = (a3 > 0.f && a3 < act_hi) ? g.w : 0.f;
-            } else if (mask_mode == 2) {
-                const float4 mk = *(const float4*)(mask_src + ((size_t)n * HW + pix) * C + c);
-                g.x = mk.x > 0.f ? g.x : 0.f; g.y = mk.y > 0.f ? g.y : 0.f; g.z = mk.z > 0.f ? g.z : 0.f; g.w = mk.w > 0.f ? g.w : 0.f;
-            }
-            *(float4*)(g_out + ((size_t)n * HW + pix) * C + c) = g;
-            if (g_copy) *(float4*)(g_copy + ((size_t)n * HW + pix) * C + c) = g;
-            s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
-            s2[0] += g.x * ((xv.x - mu.x) * rs.x); s2[1] += g.y * ((xv.y - mu.y) * rs.y);
-            s2[2] += g.z * ((xv.z - mu.z) * rs.z); s2[3] += g.w * ((xv.w - mu.w) * rs.w);
-        }
-    }
-    for (int j = 0; j < 4; ++j) { sh[0][pl][cq * 4 + j] = s1[j]; sh[1][pl][cq * 4 + j] = s2[j]; }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        int which = threadIdx.x >> 6, ch = threadIdx.x & 63;
-        float a = 0.f;
-        for (int k = 0; k < 16; ++k) a += sh[which][k][ch];
-        int cg = cb * 64 + ch;
-        if (cg < C) part[(((size_t)n * S + s) * C + cg) * 2 + which] = a;
-    }
-}
-
-__global__ __launch_bounds__(256) void adain_bwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ gamma, int ab_stride,
-                                          const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ dgamma,
-                                          float* __restrict__ dbeta, float* __restrict__ coef, int N, int C, int S, float inv_hw,
-                                          int frozen = 0) {
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;          // one wave per (n, c)
-    if (idx >= N * C) return;
-    int n = idx / C, c = idx % C;
-    double a1 = 0, a2 = 0;
-    for (int s = lane; s < S; s += 64) { const float* q = part + (((size_t)n * S + s) * C + c) * 2; a1 += q[0]; a2 += q[1]; }
-    for (int o = 32; o > 0; o >>= 1) { a1 += __shfl_down(a1, o, 64); a2 += __shfl_down(a2, o, 64); }
-    if (lane != 0) return;
-    float S1 = (float)a1, S2 = (float)a2;
-    if (dgamma) dgamma[(size_t)n * ab_stride + c] = S2;
-    if (dbeta) dbeta[(size_t)n * ab_stride + c] = S1;
-    float g = gamma ? gamma[(size_t)n * ab_stride + c] : 1.f;
-    float r = rstd[idx], m = mean[idx];
-    float ca = g * r;
-    float cb = frozen ? 0.f : -ca * r * S2 * inv_hw;          // frozen: the statistics are constants (running statistics, eval mode)
-    float cc = frozen ? 0.f : -ca * S1 * inv_hw - cb * m;
-    coef[(size_t)idx * 3 + 0] = ca; coef[(size_t)idx * 3 + 1] = cb; coef[(size_t)idx * 3 + 2] = cc;
-}
-
-// o_hi (, o_lo) | NULL: the result ALSO goes out as bf16 (hi + lo) operand planes [N][HW][C] (C % 8 == 0) -- what lp_act_pack(grad) would write in
-// the bf16 / bf16x3 modes (no gradient scale there) -- and with keep_dx == 0 ONLY as planes (round 6: the generator's backward in its bf16x3 default;
-// a conv's gradient operand then costs no fp32 round trip and no pack launch)
-template <bool X16 = false>
-__global__ void adain_bwd_apply_kernel(float* __restrict__ dx /* holds g */, const void* __restrict__ x, const float* __restrict__ add,
-                                       const float* __restrict__ coef, long long total4, int HW, int C, float* __restrict__ amax,
-                                       uint16_t* __restrict__ o_hi = nullptr, uint16_t* __restrict__ o_lo = nullptr, int keep_dx = 1) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const int C4 = C >> 2;
-    float am = 0.f;
-    for (; i < total4; i += stride) {
-        int c = (int)(i % C4) * 4;
-        int n = (int)(i / ((long long)C4 * HW));
-        const float* cf = coef + ((size_t)n * C + c) * 3;
-        float4 g = ((const float4*)dx)[i], xv = lp_ldx4<X16>(x, (size_t)i * 4), o;
-        o.x = fmaf(cf[0], g.x, fmaf(cf[1], xv.x, cf[2]));
-        o.y = fmaf(cf[3], g.y, fmaf(cf[4], xv.y, cf[5]));
-        o.z = fmaf(cf[6], g.z, fmaf(cf[7], xv.z, cf[8]));
-        o.w = fmaf(cf[9], g.w, fmaf(cf[10], xv.w, cf[11]));
-        if (add) { float4 a = ((const float4*)add)[i]; o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
-        if (keep_dx) ((float4*)dx)[i] = o;
-        if (o_hi) lp_store_bf16_planes4(o, o_hi, o_lo, (size_t)i * 4);
-        am = lp_amax4(am, o);
-    }
-    if (amax) lp_amax_commit(am, amax, blockIdx.x);
-}
-
-extern "C" long long lp_adain_bwd_workspace_bytes(int N, int HW, int C) {
-    const int PB = lp_stat_split_pix(N, HW, C);
-    long long S = (HW + PB - 1) / PB;
-    return (long long)N * S * C * 2 * 4 + (long long)N * C * 3 * 4;
-}
-
-extern "C" int lp_adain_relu_bwd(const float* dA, const float* x, const float* add, const float* gamma, int ab_stride, const float* mean,
-                                 const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                                 float* workspace, int N, int H, int W, int C, int upsample, float* amax_slots, void* stream) {
-    return lp_norm_act_bwd(dA, x, add, gamma, ab_stride, mean, rstd, scale, shift, dx, dgamma, dbeta, workspace, N, H, W, C, upsample, 0,
-                           nullptr, nullptr, 0.f, 0, amax_slots, stream);
-}
-
-static int norm_act_bwd_impl(const float* dA, const void* x, int x16, const float* add, const float* gamma, int ab_stride, const float* mean,
-                             const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                             float* workspace, int N, int H, int W, int C, int upsample, int mask_mode, const float* mask_src,
-                             float* g_copy, float act_hi, int frozen_stats, float* amax_slots, void* stream,
-                             uint16_t* o_hi = nullptr, uint16_t* o_lo = nullptr, int keep_dx = 1);
-
-// lp_adain_relu_bwd whose result goes out as bf16 (out_lo == NULL) / bf16 hi + lo operand planes [N][H][W][C] (C % 8 == 0) -- the gradient operand
-// of the conv below, in the bf16 / bf16x3 modes (no gradient scale) -- and, with keep_dx != 0, also as fp32 dx.  dx must always be given: it holds
-// the masked gradient between the passes.
-extern "C" int lp_adain_relu_bwd_planes(const float* dA, const float* x, const float* add, const float* gamma, int ab_stride, const float* mean,
-                                        const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                                        float* workspace, int N, int H, int W, int C, int upsample, uint16_t* out_hi, uint16_t* out_lo,
-                                        int keep_dx, void* stream) {
-    if (!out_hi) return lp_set_error(LP_ERR_ARG, "lp_adain_relu_bwd_planes: null pointer");
-    if (C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_adain_relu_bwd_planes: C must be a multiple of 8");
-    return norm_act_bwd_impl(dA, x, 0, add, gamma, ab_stride, mean, rstd, scale, shift, dx, dgamma, dbeta, workspace, N, H, W, C, upsample, 0,
-                             nullptr, nullptr, 0.f, 0, nullptr, stream, out_hi, out_lo, keep_dx);
-}
-
-// lp_adain_relu_bwd with x held as a 16-bit-resident conv output (fp16 plane [N][H][W][C], C % 8 == 0): the generator's fp16 mode keeps
-// no fp32 copy of its conv outputs (round 5); x-hat and the ReLU pattern are recomputed from the SAME fp16 values the forward normalised
-extern "C" int lp_adain_relu_bwd16(const float* dA, const uint16_t* x16, const float* add, const float* gamma, int ab_stride, const float* mean,
-                                   const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                                   float* workspace, int N, int H, int W, int C, int upsample, float* amax_slots, void* stream) {
-    if (C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_adain_relu_bwd16: C must be a multiple of 8");
-    return norm_act_bwd_impl(dA, x16, 1, add, gamma, ab_stride, mean, rstd, scale, shift, dx, dgamma, dbeta, workspace, N, H, W, C, upsample, 0,
-                             nullptr, nullptr, 0.f, 0, amax_slots, stream);
-}
-
-extern "C" int lp_norm_act_bwd(const float* dA, const float* x, const float* add, const float* gamma, int ab_stride, const float* mean,
-                               const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                               float* workspace, int N, int H, int W, int C, int upsample, int mask_mode, const float* mask_src,
-                               float* g_copy, float act_hi, int frozen_stats, float* amax_slots, void* stream) {
-    return norm_act_bwd_impl(dA, x, 0, add, gamma, ab_stride, mean, rstd, scale, shift, dx, dgamma, dbeta, workspace, N, H, W, C, upsample, mask_mode,
-                             mask_src, g_copy, act_hi, frozen_stats, amax_slots, stream);
-}
-
-static int norm_act_bwd_impl(const float* dA, const void* x, int x16, const float* add, const float* gamma, int ab_stride, const float* mean,
-                             const float* rstd, const float* scale, const float* shift, float* dx, float* dgamma, float* dbeta,
-                             float* workspace, int N, int H, int W, int C, int upsample, int mask_mode, const float* mask_src,
-                             float* g_copy, float act_hi, int frozen_stats, float* amax_slots, void* stream,
-                             uint16_t* o_hi, uint16_t* o_lo, int keep_dx) {
-    if (!dA || !x || !mean || !rstd || !scale || !shift || !dx || !workspace) return lp_set_error(LP_ERR_ARG, "lp_norm_act_bwd: null pointer");
-    if (C & 3) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_norm_act_bwd: C must be a multiple of 4");
-    if (mask_mode < 0 || mask_mode > 2 || (mask_mode == 2 && !mask_src)) return lp_set_error(LP_ERR_ARG, "lp_norm_act_bwd: bad mask mode");
-    if ((long long)H * W >= (1ll << 30)) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_norm_act_bwd: H*W < 2^30");
-    const int HW = H * W;
-    const int PB = lp_stat_split_pix(N, HW, C);
-    int S = (HW + PB - 1) / PB;
-    float* part = workspace;
-    float* coef = workspace + (size_t)N * S * C * 2;
-    hipStream_t st = (hipStream_t)stream;
-    if (x16) hipLaunchKernelGGL(adain_bwd_partial_kernel<true>, dim3(S, (C + 63) / 64, N), dim3(256), 0, st, dA, x, mean, rstd, scale, shift, dx, part,
-                                H, W, C, upsample, S, PB, mask_mode, mask_src, g_copy, act_hi > 0.f ? act_hi : 3.0e38f);
-    else hipLaunchKernelGGL(adain_bwd_partial_kernel<false>, dim3(S, (C + 63) / 64, N), dim3(256), 0, st, dA, x, mean, rstd, scale, shift, dx, part,
-                            H, W, C, upsample, S, PB, mask_mode, mask_src, g_copy, act_hi > 0.f ? act_hi : 3.0e38f);
-    int rc = lp_check_launch("adain_bwd_partial");
-    if (rc) return rc;
-    hipLaunchKernelGGL(adain_bwd_finalize_kernel, dim3(cdiv((long long)N * C, 4)), dim3(256), 0, st, part, gamma, ab_stride, mean, rstd,
-                       dgamma, dbeta, coef, N, C, S, 1.0f / (float)HW, frozen_stats);
-    rc = lp_check_launch("adain_bwd_finalize");
-    if (rc) return rc;
-    long long total4 = (long long)N * HW * C / 4;
-    int blocks = (int)((total4 + 255) / 256); if (blocks > 4096) blocks = 4096;
-    if (x16) hipLaunchKernelGGL(adain_bwd_apply_kernel<true>, dim3(blocks), dim3(256), 0, st, dx, x, add, coef, total4, HW, C, amax_slots, o_hi, o_lo, keep_dx);
-    else hipLaunchKernelGGL(adain_bwd_apply_kernel<false>, dim3(blocks), dim3(256), 0, st, dx, x, add, coef, total4, HW, C, amax_slots, o_hi, o_lo, keep_dx);
-    return lp_check_launch("adain_bwd_apply");
 }
 
 // ------------------------------------------------------------------------------------------------------------------

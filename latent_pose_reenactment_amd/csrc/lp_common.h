@@ -67,6 +67,68 @@ __device__ __forceinline__ void lp_amax_commit(float m, float* slots, unsigned k
     }
 }
 
+// amax -> power-of-two input scale of an fp16 gradient operand: s = 2^(13 - e) with amax = f * 2^e, f in [0.5, 1): the scaled
+// tensor's amax lands in [2^12, 2^13) -- 3 binades of headroom below the fp16 maximum, 26 binades of normal range below
+__device__ __forceinline__ void amax_to_scale(float m, float& s, float& inv) {
+    s = 1.f; inv = 1.f;
+    if (m > 0.f && m < 3.0e38f) {
+        int e;
+        (void)frexpf(m, &e);
+        int k = 13 - e;
+        k = k > 100 ? 100 : (k < -100 ? -100 : k);
+        s = ldexpf(1.f, k); inv = ldexpf(1.f, -k);
+    }
+}
+
+// ---- 8 (4) consecutive channels as fp32 <-> 16-bit operand planes ------------------------------------------------------------------
+template <bool F16, bool SPLIT>
+__device__ __forceinline__ void store_op8(const float (&v)[8], uint16_t* hi, uint16_t* lo, size_t off8) {
+    s16x8_t h, l;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint16_t hb = lp_f32_to_op16<F16>(v[j]);
+        h[j] = (short)hb;
+        if (SPLIT) l[j] = (short)lp_f32_to_op16<false>(v[j] - lp_op16_to_f32<false>(hb));
+    }
+    *(s16x8_t*)(hi + off8) = h;
+    if (SPLIT) *(s16x8_t*)(lo + off8) = l;
+}
+
+// 8 consecutive channels of a tensor that lives either as fp32 or -- the fp16 mode's 16-bit-resident conv outputs ("y16": the unscaled
+// fp16 plane the conv epilogue wrote instead of fp32 y) -- as one fp16 operand plane
+template <bool H16> __device__ __forceinline__ void load8(const void* base, size_t off, float (&v)[8]) {
+    if (H16) {
+        const s16x8_t q = *(const s16x8_t*)((const uint16_t*)base + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = lp_op16_to_f32<true>((uint16_t)q[j]);
+    } else {
+        const float4 a = *(const float4*)((const float*)base + off), b = *(const float4*)((const float*)base + off + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    }
+}
+// the 4-wide forms of the fp32 NHWC kernels (C % 4 == 0): x as fp32 or as a 16-bit-resident conv output (C % 8 == 0)
+template <bool X16> __device__ __forceinline__ float4 lp_ldx4(const void* x, size_t e) {
+    if (X16) {
+        const ushort4 h = *(const ushort4*)((const uint16_t*)x + e);
+        return make_float4(lp_op16_to_f32<true>(h.x), lp_op16_to_f32<true>(h.y), lp_op16_to_f32<true>(h.z), lp_op16_to_f32<true>(h.w));
+    }
+    return *(const float4*)((const float*)x + e);
+}
+
+// four consecutive channels of a gradient tensor as bf16 operand planes: hi = RNE bf16, lo = bf16(v - hi) (|NULL: plain bf16 mode)
+__device__ __forceinline__ void lp_store_bf16_planes4(const float4& o, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, size_t e) {
+    const float v[4] = {o.x, o.y, o.z, o.w};
+    ushort4 h, l;
+    uint16_t* hp = (uint16_t*)&h; uint16_t* lp = (uint16_t*)&l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        hp[j] = lp_f32_to_op16<false>(v[j]);
+        lp[j] = lp_f32_to_op16<false>(v[j] - lp_op16_to_f32<false>(hp[j]));
+    }
+    *(ushort4*)(hi + e) = h;
+    if (lo) *(ushort4*)(lo + e) = l;
+}
+
 __device__ __forceinline__ void lp_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 template <int N> __device__ __forceinline__ void lp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N) : "memory"); }
 

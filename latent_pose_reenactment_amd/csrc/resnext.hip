@@ -7,8 +7,8 @@
 //   * lp_spatial_mean      AdaptiveAvgPool2d(1) forward / backward
 //   * lp_pack_grouped      weight image of the block-diagonal grouped 3x3 conv (lp_gconv16_fwd)
 // The contractions themselves (1x1 convs, the grouped 3x3, the stem on its im2col rows, the classifier) run on conv_dma.hip /
-// conv_wgrad.hip; the BatchNorm statistics and BatchNorm backward on the instance-norm kernels of elementwise.hip (a BatchNorm over
-// [P][C] is an instance norm with one "image" of P pixels).
+// conv_wgrad.hip; the BatchNorm statistics on the instance-norm kernels of elementwise.hip (a BatchNorm over [P][C] is an instance
+// norm with one "image" of P pixels) and the BatchNorm backward (lp_norm_act_bwd, lp_bn_bwd16) in norm_bwd.hip.
 #include "lp_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
@@ -16,38 +16,6 @@
 static inline unsigned grid_for(long long items, int cap = 16384) {
     long long b = (items + 255) / 256;
     return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
-}
-
-template <bool F16, bool SPLIT>
-__device__ __forceinline__ void store_op8(const float (&v)[8], uint16_t* hi, uint16_t* lo, size_t off8) {
-    s16x8_t h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint16_t hb = lp_f32_to_op16<F16>(v[j]);
-        h[j] = (short)hb;
-        if (SPLIT) l[j] = (short)lp_f32_to_op16<false>(v[j] - lp_op16_to_f32<false>(hb));
-    }
-    *(s16x8_t*)(hi + off8) = h;
-    if (SPLIT) *(s16x8_t*)(lo + off8) = l;
-}
-
-// 8 consecutive channels of a tensor that lives either as fp32 or -- the fp16 mode's 16-bit-resident conv outputs ("y16": the unscaled
-// fp16 plane the conv epilogue wrote instead of fp32 y) -- as one fp16 operand plane
-template <bool H16> __device__ __forceinline__ void load8(const void* base, size_t off, float (&v)[8]) {
-    if (H16) {
-        const s16x8_t q = *(const s16x8_t*)((const uint16_t*)base + off);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = lp_op16_to_f32<true>((uint16_t)q[j]);
-    } else {
-        const float4 a = *(const float4*)((const float*)base + off), b = *(const float4*)((const float*)base + off + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-}
-// ReLU pattern of 8 channels from a 16-bit plane: > 0  <=>  sign clear and magnitude non-zero
-__device__ __forceinline__ void mask8_16(const uint16_t* plane, size_t off, float (&g)[8]) {
-    const s16x8_t q = *(const s16x8_t*)(plane + off);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = ((unsigned)((uint16_t)q[j]) - 1u) < 0x7fffu ? g[j] : 0.f;
 }
 
 // ---- im2col rows as operand planes -----------------------------------------------------------------------------------------------
@@ -508,313 +476,4 @@ extern "C" int lp_pack_grouped(const float* w, uint16_t* hi, uint16_t* lo, int C
     const long long total = 9ll * CP * 64;
     hipLaunchKernelGGL(pack_grouped_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, w, hi, f16 ? nullptr : lo, C, group_size, CP, mode, f16, total);
     return lp_check_launch("pack_grouped");
-}
-
-// ---- BatchNorm (+ activation) backward straight to operand planes ------------------------------------------------------------------
-// The embedder's conv -> BatchNorm -> ReLU chains only ever consume the BatchNorm input gradient dy as the 16-bit operand of the weight /
-// data gradient contractions, so it is never written in fp32:
-//   pass 1 (partial):  per (pixel split, channel)  S1 = sum g, S2 = sum g*xhat, max|g|, max|xhat|     g = dA * activation mask (recomputed, not stored)
-//   pass 2 (finalize): dgamma = S2, dbeta = S1, coefficients of dy = ca*g + cb*x + cc, and a per-channel BOUND of |dy|
-//                      (|ca| * (max|g| + |S1|/P + max|xhat| * |S2|/P)) from which the fp16 gradient scale is taken (a power of two putting the
-//                      bound into [2^12, 2^13): the true amax is at most the bound, so the scaled planes cannot overflow)
-//   pass 3 (apply):    recomputes g from dA and the mask, writes dy * s as operand planes (hi [, lo]); block 0 publishes {s, 1/s}
-// 8 B read in pass 1 and 8 B read + 2 B written in pass 3 per element (fp16 mode), against 30 B for partial + apply + lp_act_pack on fp32 dy.
-// mask modes as lp_norm_act_bwd: 0 own activation 0 < x*scale+shift < act_hi, 1 none, 2 mask_src > 0; 3: a 16-bit operand plane > 0.
-// X16: x is the fp16 plane of a 16-bit-resident conv output (6 B read per element and pass instead of 8 B).
-template <bool X16>
-__global__ __launch_bounds__(256) void bn_bwd16_partial_kernel(const float* __restrict__ dA, const void* __restrict__ x, const void* __restrict__ mask_src,
-                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                               const float* __restrict__ scale, const float* __restrict__ shift,
-                                                               float* __restrict__ part, long long P, int C, int mask_mode, float act_hi, int PB) {
-    __shared__ float sh[4][16][64];
-    const int cb = blockIdx.y, s = blockIdx.x;
-    const int cq = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int c = cb * 64 + cq * 4;
-    const long long p0 = (long long)s * PB, p1 = min(P, p0 + PB);
-    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0}, gm[4] = {0, 0, 0, 0}, xm[4] = {0, 0, 0, 0};
-    if (c < C) {
-        const float4 mu = *(const float4*)(mean + c), rs = *(const float4*)(rstd + c);
-        const float4 sc = *(const float4*)(scale + c), sf = *(const float4*)(shift + c);
-        const float m4[4] = {mu.x, mu.y, mu.z, mu.w}, r4[4] = {rs.x, rs.y, rs.z, rs.w}, a4[4] = {sc.x, sc.y, sc.z, sc.w}, b4[4] = {sf.x, sf.y, sf.z, sf.w};
-#pragma unroll 4
-        for (long long pix = p0 + pl; pix < p1; pix += 16) {
-            const float4 gv = *(const float4*)(dA + pix * C + c);
-            float xs[4], g[4] = {gv.x, gv.y, gv.z, gv.w};
-            if (X16) {
-                const s16x4_t q = *(const s16x4_t*)((const uint16_t*)x + pix * C + c);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xs[j] = lp_op16_to_f32<true>((uint16_t)q[j]);
-            } else {
-                const float4 xv = *(const float4*)((const float*)x + pix * C + c);
-                xs[0] = xv.x; xs[1] = xv.y; xs[2] = xv.z; xs[3] = xv.w;
-            }
-            if (mask_mode == 2) {
-                const float4 mk = *(const float4*)((const float*)mask_src + pix * C + c);
-                const float k4[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) g[j] = k4[j] > 0.f ? g[j] : 0.f;
-            } else if (mask_mode == 3) {
-                const s16x4_t mk = *(const s16x4_t*)((const uint16_t*)mask_src + pix * C + c);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) g[j] = ((unsigned)((uint16_t)mk[j]) - 1u) < 0x7fffu ? g[j] : 0.f;
-            } else if (mask_mode == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float a = fmaf(xs[j], a4[j], b4[j]); g[j] = (a > 0.f && a < act_hi) ? g[j] : 0.f; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = (xs[j] - m4[j]) * r4[j];
-                s1[j] += g[j]; s2[j] = fmaf(g[j], xh, s2[j]);
-                gm[j] = fmaxf(gm[j], fabsf(g[j])); xm[j] = fmaxf(xm[j], fabsf(xh));
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { sh[0][pl][cq * 4 + j] = s1[j]; sh[1][pl][cq * 4 + j] = s2[j]; sh[2][pl][cq * 4 + j] = gm[j]; sh[3][pl][cq * 4 + j] = xm[j]; }
-    __syncthreads();
-    {
-        const int which = threadIdx.x >> 6, ch = threadIdx.x & 63;
-        float a = 0.f;
-        if (which < 2) { for (int k = 0; k < 16; ++k) a += sh[which][k][ch]; }
-        else { for (int k = 0; k < 16; ++k) a = fmaxf(a, sh[which][k][ch]); }
-        const int cg = cb * 64 + ch;
-        if (cg < C) part[((size_t)s * C + cg) * 4 + which] = a;
-    }
-}
-
-// one wave per channel: merges the S partials; coef[c] = {ca, cb, cc}, bound[c] >= max|dy| of the channel
-__global__ __launch_bounds__(256) void bn_bwd16_finalize_kernel(const float* __restrict__ part, const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                                const float* __restrict__ rstd, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                float* __restrict__ coef, float* __restrict__ bound, int C, int S, float inv_p, int frozen) {
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (c >= C) return;
-    double a1 = 0, a2 = 0;
-    float gm = 0.f, xm = 0.f;
-    for (int s = lane; s < S; s += 64) {
-        const float* q = part + ((size_t)s * C + c) * 4;
-        a1 += q[0]; a2 += q[1]; gm = fmaxf(gm, q[2]); xm = fmaxf(xm, q[3]);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        a1 += __shfl_down(a1, o, 64); a2 += __shfl_down(a2, o, 64);
-        gm = fmaxf(gm, __shfl_down(gm, o, 64)); xm = fmaxf(xm, __shfl_down(xm, o, 64));
-    }
-    if (lane != 0) return;
-    const float S1 = (float)a1, S2 = (float)a2;
-    dgamma[c] = S2; dbeta[c] = S1;
-    const float r = rstd[c], m = mean[c], ca = gamma[c] * r;
-    const float cb = frozen ? 0.f : -ca * r * S2 * inv_p;
-    const float cc = frozen ? 0.f : -ca * S1 * inv_p - cb * m;
-    coef[c * 3 + 0] = ca; coef[c * 3 + 1] = cb; coef[c * 3 + 2] = cc;
-    bound[c] = frozen ? fabsf(ca) * gm : fabsf(ca) * (gm + fabsf(S1) * inv_p + xm * fabsf(S2) * inv_p);
-}
-
-template <int PREC, bool X16>
-__global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const float* __restrict__ dA, const void* __restrict__ x, const void* __restrict__ mask_src,
-                                                             const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ coef,
-                                                             const float* __restrict__ bound, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                             float* __restrict__ out_scale, long long items, int C, int mask_mode, float act_hi,
-                                                             float* __restrict__ g_out) {
-    constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
-    float sc_out = 1.f;
-    if (F16) {       // every block derives the same power-of-two scale from the per-channel bounds (C floats, L2 resident)
-        __shared__ float shm[4];
-        float m = 0.f;
-        for (int j = threadIdx.x; j < C; j += 256) m = fmaxf(m, bound[j]);
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-        if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
-        __syncthreads();
-        m = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
-        float inv = 1.f;
-        if (m > 0.f && m < 3.0e38f) {
-            int e;
-            (void)frexpf(m, &e);
-            int k = 13 - e;
-            k = k > 100 ? 100 : (k < -100 ? -100 : k);
-            sc_out = ldexpf(1.f, k); inv = ldexpf(1.f, -k);
-        }
-        if (out_scale && blockIdx.x == 0 && threadIdx.x == 0) { out_scale[0] = sc_out; out_scale[1] = inv; }
-    } else if (out_scale && blockIdx.x == 0 && threadIdx.x == 0) { out_scale[0] = 1.f; out_scale[1] = 1.f; }
-    const int G = C >> 3;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % G) * 8;
-        const float4 g0 = *(const float4*)(dA + i * 8), g1 = *(const float4*)(dA + i * 8 + 4);
-        float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, xs[8];
-        load8<X16>(x, (size_t)i * 8, xs);
-        if (mask_mode == 2) {
-            float k8[8];
-            load8<false>(mask_src, (size_t)i * 8, k8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = k8[j] > 0.f ? g[j] : 0.f;
-        } else if (mask_mode == 3) {
-            mask8_16((const uint16_t*)mask_src, (size_t)i * 8, g);
-        } else if (mask_mode == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float a = fmaf(xs[j], scale[c + j], shift[c + j]); g[j] = (a > 0.f && a < act_hi) ? g[j] : 0.f; }
-        }
-        if (g_out) {          // the masked incoming gradient itself: what the identity branch of a residual block receives
-            *(float4*)(g_out + i * 8) = make_float4(g[0], g[1], g[2], g[3]);
-            *(float4*)(g_out + i * 8 + 4) = make_float4(g[4], g[5], g[6], g[7]);
-        }
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float* cf = coef + (c + j) * 3;
-            v[j] = fmaf(cf[0], g[j], fmaf(cf[1], xs[j], cf[2])) * sc_out;
-        }
-        store_op8<F16, SPLIT>(v, hi, lo, (size_t)i * 8);
-    }
-}
-
-// pass 3 for C/8 <= 256 channel groups (every layer of the two encoders): a thread keeps ONE group of 8 channels -- its 40 coefficients
-// (ca, cb, cc, scale, shift) are loaded once as float4s -- and walks the pixels of its block (256 / (C/8) pixels per iteration, the
-// lanes of a pixel contiguous: coalesced 32 B per lane).  The one-item-per-thread form above re-reads 40 scalars per 8 elements.
-template <int PREC, bool X16>
-__global__ __launch_bounds__(256) void bn_bwd16_apply_rows_kernel(const float* __restrict__ dA, const void* __restrict__ x, const void* __restrict__ mask_src,
-                                                                  const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ coef,
-                                                                  const float* __restrict__ bound, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                                  float* __restrict__ out_scale, long long P, int C, int rows, int PB, int mask_mode, float act_hi,
-                                                                  float* __restrict__ g_out) {
-    constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
-    float sc_out = 1.f;
-    if (F16) {
-        __shared__ float shm[4];
-        float m = 0.f;
-        for (int j = threadIdx.x; j < C; j += 256) m = fmaxf(m, bound[j]);
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-        if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
-        __syncthreads();
-        m = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
-        float inv = 1.f;
-        if (m > 0.f && m < 3.0e38f) {
-            int e;
-            (void)frexpf(m, &e);
-            int k = 13 - e;
-            k = k > 100 ? 100 : (k < -100 ? -100 : k);
-            sc_out = ldexpf(1.f, k); inv = ldexpf(1.f, -k);
-        }
-        if (out_scale && blockIdx.x == 0 && threadIdx.x == 0) { out_scale[0] = sc_out; out_scale[1] = inv; }
-    } else if (out_scale && blockIdx.x == 0 && threadIdx.x == 0) { out_scale[0] = 1.f; out_scale[1] = 1.f; }
-    const int G = C >> 3;
-    const int cg = threadIdx.x % G, r = threadIdx.x / G;
-    if (r >= rows) return;
-    const int c = cg * 8;
-    float cf[24], a8[8], b8[8];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) { const float4 q = *(const float4*)(coef + (size_t)c * 3 + j * 4); cf[j * 4] = q.x; cf[j * 4 + 1] = q.y; cf[j * 4 + 2] = q.z; cf[j * 4 + 3] = q.w; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float4 q = *(const float4*)(scale + c + j * 4), t = *(const float4*)(shift + c + j * 4);
-        a8[j * 4] = q.x; a8[j * 4 + 1] = q.y; a8[j * 4 + 2] = q.z; a8[j * 4 + 3] = q.w;
-        b8[j * 4] = t.x; b8[j * 4 + 1] = t.y; b8[j * 4 + 2] = t.z; b8[j * 4 + 3] = t.w;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { cf[j * 3] *= sc_out; cf[j * 3 + 1] *= sc_out; cf[j * 3 + 2] *= sc_out; }      // power of two: exact
-    const long long p0 = (long long)blockIdx.x * PB, p1 = min(P, p0 + PB);
-#pragma unroll 2
-    for (long long pix = p0 + r; pix < p1; pix += rows) {
-        const size_t off = (size_t)pix * C + c;
-        const float4 g0 = *(const float4*)(dA + off), g1 = *(const float4*)(dA + off + 4);
-        float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, xs[8];
-        load8<X16>(x, off, xs);
-        if (mask_mode == 2) {
-            float k8[8];
-            load8<false>(mask_src, off, k8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = k8[j] > 0.f ? g[j] : 0.f;
-        } else if (mask_mode == 3) {
-            mask8_16((const uint16_t*)mask_src, off, g);
-        } else if (mask_mode == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float a = fmaf(xs[j], a8[j], b8[j]); g[j] = (a > 0.f && a < act_hi) ? g[j] : 0.f; }
-        }
-        if (g_out) {
-            *(float4*)(g_out + off) = make_float4(g[0], g[1], g[2], g[3]);
-            *(float4*)(g_out + off + 4) = make_float4(g[4], g[5], g[6], g[7]);
-        }
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaf(cf[j * 3], g[j], fmaf(cf[j * 3 + 1], xs[j], cf[j * 3 + 2]));
-        store_op8<F16, SPLIT>(v, hi, lo, off);
-    }
-}
-
-extern "C" long long lp_bn_bwd16_workspace_bytes(long long P, int C) {
-    const int PB = lp_stat_split_pix(1, P, C);
-    const long long S = (P + PB - 1) / PB;
-    return (S * C * 4 + (long long)C * 4) * (long long)sizeof(float);
-}
-
-static int bn_bwd16_impl(const float* dA, const float* x, const uint16_t* x16, const void* mask_src, const float* gamma, const float* mean,
-                         const float* rstd, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo, float* out_scale,
-                         float* dgamma, float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats,
-                         int prec, float* g_out, hipStream_t st) {
-    if (!dA || (!x && !x16) || !gamma || !mean || !rstd || !scale || !shift || !out_hi || !out_scale || !dgamma || !dbeta || !workspace)
-        return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: null pointer");
-    if (C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16: C must be a multiple of 8");
-    if (mask_mode < 0 || mask_mode > 3 || (mask_mode >= 2 && !mask_src)) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: bad mask mode");
-    if (prec == LP_PREC_BF16X3 && !out_lo) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: bf16x3 needs the lo plane");
-    if (x16 && prec != LP_PREC_F16) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16_h: 16-bit x exists in the fp16 mode only");
-    if (P < 1) return LP_OK;
-    const int PB = lp_stat_split_pix(1, P, C);
-    const int S = (int)((P + PB - 1) / PB);
-    float* part = workspace;
-    float* coef = workspace + (size_t)S * C * 4;
-    float* bound = coef + (size_t)C * 3;
-    const float hi_ = act_hi > 0.f ? act_hi : 3.0e38f;
-    const void* xv = x16 ? (const void*)x16 : (const void*)x;
-    if (x16) hipLaunchKernelGGL(bn_bwd16_partial_kernel<true>, dim3(S, (C + 63) / 64), dim3(256), 0, st, dA, xv, mask_src, mean, rstd, scale, shift, part, P, C, mask_mode, hi_, PB);
-    else hipLaunchKernelGGL(bn_bwd16_partial_kernel<false>, dim3(S, (C + 63) / 64), dim3(256), 0, st, dA, xv, mask_src, mean, rstd, scale, shift, part, P, C, mask_mode, hi_, PB);
-    int rc = lp_check_launch("bn_bwd16_partial");
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd16_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, gamma, mean, rstd, dgamma, dbeta, coef, bound, C, S,
-                       1.0f / (float)P, frozen_stats);
-    rc = lp_check_launch("bn_bwd16_finalize");
-    if (rc) return rc;
-    const long long items = P * (C >> 3);
-    const int G = C >> 3;
-    static const bool one_item = getenv("LP_BNB_ITEMS") != nullptr;          // A/B knob: the one-item-per-thread form
-    if (G <= 256 && !one_item) {
-        const int rows = 256 / G;
-        long long ppb = (P + 4095) / 4096;                                   // <= 4096 workgroups, >= 4 pixel rows per thread where P allows
-        if (ppb < 4ll * rows) ppb = 4ll * rows;
-        ppb = (ppb + rows - 1) / rows * rows;
-        const unsigned grid = (unsigned)((P + ppb - 1) / ppb);
-#define LP_BR(Q, H) hipLaunchKernelGGL((bn_bwd16_apply_rows_kernel<Q, H>), dim3(grid), dim3(256), 0, st, dA, xv, mask_src, scale, shift, coef, bound, out_hi, out_lo, out_scale, P, C, rows, (int)ppb, mask_mode, hi_, g_out)
-        if (x16) LP_BR(LP_PREC_F16, true);
-        else if (prec == LP_PREC_BF16) LP_BR(LP_PREC_BF16, false);
-        else if (prec == LP_PREC_BF16X3) LP_BR(LP_PREC_BF16X3, false);
-        else if (prec == LP_PREC_F16) LP_BR(LP_PREC_F16, false);
-        else return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: unknown precision mode");
-#undef LP_BR
-        return lp_check_launch("bn_bwd16_apply");
-    }
-#define LP_BB(Q, H) hipLaunchKernelGGL((bn_bwd16_apply_kernel<Q, H>), dim3(grid_for(items, 8192)), dim3(256), 0, st, dA, xv, mask_src, scale, shift, coef, bound, out_hi, out_lo, out_scale, items, C, mask_mode, hi_, g_out)
-    if (x16) LP_BB(LP_PREC_F16, true);
-    else if (prec == LP_PREC_BF16) LP_BB(LP_PREC_BF16, false);
-    else if (prec == LP_PREC_BF16X3) LP_BB(LP_PREC_BF16X3, false);
-    else if (prec == LP_PREC_F16) LP_BB(LP_PREC_F16, false);
-    else return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: unknown precision mode");
-#undef LP_BB
-    return lp_check_launch("bn_bwd16_apply");
-}
-
-extern "C" int lp_bn_bwd16(const float* dA, const float* x, const float* mask_src, const float* gamma, const float* mean, const float* rstd,
-                           const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo, float* out_scale, float* dgamma,
-                           float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats, int prec,
-                           float* g_out, void* stream) {
-    if (!x) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: null pointer");
-    if (mask_mode == 3) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: mask mode 3 (16-bit plane) is lp_bn_bwd16_h's");
-    return bn_bwd16_impl(dA, x, nullptr, mask_src, gamma, mean, rstd, scale, shift, out_hi, out_lo, out_scale, dgamma, dbeta, workspace, P, C,
-                         mask_mode, act_hi, frozen_stats, prec, g_out, (hipStream_t)stream);
-}
-
-// x as fp32 (x16 = NULL) or as the fp16 plane a conv epilogue wrote instead of fp32 y (x = NULL, fp16 mode); mask modes 0 / 1 / 2 as
-// lp_bn_bwd16 (2: mask_src fp32 > 0) and 3: mask_src = a 16-bit OPERAND PLANE [P][C] whose elements are > 0 (the block output's planes:
-// 2 B instead of 4 B per element for the ReLU pattern behind the residual add)
-extern "C" int lp_bn_bwd16_h(const float* dA, const float* x, const uint16_t* x16, const void* mask_src, const float* gamma, const float* mean,
-                             const float* rstd, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo, float* out_scale,
-                             float* dgamma, float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats,
-                             int prec, float* g_out, void* stream) {
-    return bn_bwd16_impl(dA, x, x16, mask_src, gamma, mean, rstd, scale, shift, out_hi, out_lo, out_scale, dgamma, dbeta, workspace, P, C,
-                         mask_mode, act_hi, frozen_stats, prec, g_out, (hipStream_t)stream);
 }

@@ -948,20 +948,6 @@ def adain_relu_bwd(dA: Tensor, x: Tensor, add: Optional[Tensor], gamma: Tensor, 
     ``planes`` = PREC_BF16 | PREC_BF16X3 (round 6): the result ALSO leaves as that mode's gradient operand planes, written by the same launch
     (lp_adain_relu_bwd_planes; no scale in those modes) -> (dx | None, Act16); ``keep_dx=False``: planes only."""
     _chk(dA, 'dA')
-    if planes is not None and planes_direct_ok(planes, x, x.shape[3] if not isinstance(x, Act16) else 0):
-        n, h, w, c = x.shape
-        assert dA.shape == (n, h << int(upsample), w << int(upsample), c), (dA.shape, (n, h, w, c))
-        assert gamma.stride(1) == 1 and dgamma.stride(1) == 1 and dbeta.stride(1) == 1 and gamma.stride(0) == dgamma.stride(0) == dbeta.stride(0)
-        dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dA.device)          # (holds the masked gradient between the passes)
-        ws = torch.empty(_lib.lib().lp_adain_bwd_workspace_bytes(n, h * w, c) // 4, dtype=torch.float32, device=dA.device)
-        o_hi, o_lo = _alloc16(n, h, w, c, planes, dA.device)
-        check(_lib.lib().lp_adain_relu_bwd_planes(dA.data_ptr(), x.data_ptr(), _p(add), gamma.data_ptr(), gamma.stride(0), mean.data_ptr(), rstd.data_ptr(),
-                                                  scale.data_ptr(), shift.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
-                                                  n, h, w, c, int(upsample), o_hi.data_ptr(), _p(o_lo), int(keep_dx), _stream()), 'lp_adain_relu_bwd_planes')
-        return (dx if keep_dx else None), Act16(o_hi, o_lo, c, None)
-    if planes is not None:          # (geometry the fused form does not cover: the two-launch form)
-        dx = adain_relu_bwd(dA, x, add, gamma, mean, rstd, scale, shift, dgamma, dbeta, upsample, amax=amax)
-        return dx, act_pack(dx, prec=planes, grad=True)
     x16 = x if isinstance(x, Act16) else None          # 16-bit-resident conv output (the generator's fp16 mode: no fp32 copy of x exists)
     if x16 is not None:
         assert x16.lo is None and x16.inv is None and x16.hi.shape[3] == x16.c, 'a 16-bit-resident x is ONE unscaled fp16 plane with C % 8 == 0'
@@ -969,15 +955,22 @@ def adain_relu_bwd(dA: Tensor, x: Tensor, add: Optional[Tensor], gamma: Tensor, 
     else:
         _chk(x, 'x')
         n, h, w, c = x.shape
+    if planes is not None and not planes_direct_ok(planes, x, c):          # (geometry the fused form does not cover: the two-launch form)
+        dx = adain_relu_bwd(dA, x, add, gamma, mean, rstd, scale, shift, dgamma, dbeta, upsample, amax=amax)
+        return dx, act_pack(dx, prec=planes, grad=True)
     assert dA.shape == (n, h << int(upsample), w << int(upsample), c), (dA.shape, (n, h, w, c))
     assert gamma.stride(1) == 1 and dgamma.stride(1) == 1 and dbeta.stride(1) == 1
     assert gamma.stride(0) == dgamma.stride(0) == dbeta.stride(0)
-    dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dA.device)
+    dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dA.device)          # (holds the masked gradient between the passes)
     ws = torch.empty(_lib.lib().lp_adain_bwd_workspace_bytes(n, h * w, c) // 4, dtype=torch.float32, device=dA.device)
-    fn, xp, nm = (_lib.lib().lp_adain_relu_bwd, x.data_ptr(), 'lp_adain_relu_bwd') if x16 is None else \
-        (_lib.lib().lp_adain_relu_bwd16, x16.hi.data_ptr(), 'lp_adain_relu_bwd16')
-    check(fn(dA.data_ptr(), xp, _p(add), gamma.data_ptr(), gamma.stride(0), mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-             dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), n, h, w, c, int(upsample), _p(_amax_attach(dx, amax)), _stream()), nm)
+    args = (dA.data_ptr(), (x if x16 is None else x16.hi).data_ptr(), _p(add), gamma.data_ptr(), gamma.stride(0), mean.data_ptr(), rstd.data_ptr(),
+            scale.data_ptr(), shift.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), n, h, w, c, int(upsample))
+    if planes is not None:
+        o_hi, o_lo = _alloc16(n, h, w, c, planes, dA.device)
+        check(_lib.lib().lp_adain_relu_bwd_planes(*args, o_hi.data_ptr(), _p(o_lo), int(keep_dx), _stream()), 'lp_adain_relu_bwd_planes')
+        return (dx if keep_dx else None), Act16(o_hi, o_lo, c, None)
+    fn, nm = (_lib.lib().lp_adain_relu_bwd, 'lp_adain_relu_bwd') if x16 is None else (_lib.lib().lp_adain_relu_bwd16, 'lp_adain_relu_bwd16')
+    check(fn(*args, _p(_amax_attach(dx, amax)), _stream()), nm)
     return dx
 
 
@@ -1311,7 +1304,7 @@ def l1_bwd(a: Optional[Tensor], b: Optional[Tensor], grad_out: Tensor, coef: flo
 
 
 
-# ---- ResNeXt-50 identity encoder: BatchNorm statistics / backward, grouped 3x3 conv, stem, pooling (csrc/resnext.hip) -------------
+# ---- ResNeXt-50 identity encoder: BatchNorm statistics, grouped 3x3 conv, stem, pooling (csrc/resnext.hip); BatchNorm backward (csrc/norm_bwd.hip) ----
 def flat_hw(p: int) -> Tuple[int, int]:
     """(H, W) factorisation of P pixels for the 1x1 contractions (they do not care about the spatial structure): the widest W in
     {16, 8, 4} with H >= 2"""
@@ -1343,24 +1336,33 @@ def bn_train_stats(y: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optiona
     return out[0], out[1], out[2], out[3]
 
 
+def _flat_pc(dA: Tensor, x, mask_src):
+    """the [P][C] view of the norm-backward operands: -> (shape, P, C, data pointer of mask_src | None).  ``x`` / ``mask_src``: fp32 tensors of
+    dA's shape or the 16-bit plane of that shape (``Act16``; x: one unscaled fp16 plane)"""
+    _chk(dA, 'dA')
+    for t, name in ((x, 'x'), (mask_src, 'mask_src')):
+        if isinstance(t, Act16):
+            assert t.hi.shape == dA.shape, (name, t.hi.shape, dA.shape)
+        elif t is not None:
+            _chk(t, name); assert t.shape == dA.shape, (name, t.shape, dA.shape)
+    c = dA.shape[-1]
+    return dA.shape, dA.numel() // c, c, _p(mask_src.hi if isinstance(mask_src, Act16) else mask_src)
+
+
 def norm_act_bwd(dA: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, scale: Tensor, shift: Tensor, *, mask_mode: int = 0,
                  mask_src: Optional[Tensor] = None, want_g: bool = False, act_hi: float = 0.0, frozen: bool = False, amax: bool = False):
     """backward of act(BatchNorm(x)) over x [..., C] treated as [P][C] (per-channel statistics [C]):
     -> (dx, dgamma [C], dbeta [C], g | None).  mask_mode 0: act = ReLU (act_hi = 6: ReLU6) of the layer's own affine; 1: no activation;
     2: ReLU pattern taken from ``mask_src`` (the residual block's output).  ``want_g``: also return the masked incoming gradient."""
-    _chk(dA, 'dA'); _chk(x, 'x')
-    c = x.shape[-1]
-    p = x.numel() // c
-    assert dA.shape == x.shape, (dA.shape, x.shape)
+    assert not isinstance(x, Act16) and not isinstance(mask_src, Act16), 'fp32 operands only (the 16-bit forms are bn_bwd16\'s)'
+    _, p, c, mptr = _flat_pc(dA, x, mask_src)
     dx = torch.empty_like(x)
     dgb = torch.empty(2, c, dtype=torch.float32, device=x.device)
     g = torch.empty_like(x) if want_g else None
     ws = torch.empty(_lib.lib().lp_adain_bwd_workspace_bytes(1, p, c) // 4, dtype=torch.float32, device=x.device)
-    if mask_src is not None:
-        _chk(mask_src, 'mask_src'); assert mask_src.shape == x.shape
     check(_lib.lib().lp_norm_act_bwd(dA.data_ptr(), x.data_ptr(), None, gamma.data_ptr(), c, mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(),
                                      shift.data_ptr(), dx.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(), ws.data_ptr(), 1, p, 1, c, 0,
-                                     mask_mode, _p(mask_src), _p(g), float(act_hi), int(frozen), _p(_amax_attach(dx, amax)), _stream()),
+                                     mask_mode, mptr, _p(g), float(act_hi), int(frozen), _p(_amax_attach(dx, amax)), _stream()),
           'lp_norm_act_bwd')
     return dx, dgb[0], dgb[1], g
 
@@ -1692,17 +1694,12 @@ def bn_bwd16(dA: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, s
     contractions consume): -> (Act16 of dy, dgamma [C], dbeta [C], g | None).  No fp32 dy, no masked-gradient temporary; in fp16 mode the
     planes carry the power-of-two scale of lp_bn_bwd16 (``Act16.inv``).  Arguments as ``norm_act_bwd``; ``x`` may be a 16-bit-resident
     conv output (``Act16``, fp16 mode) and ``mask_src`` (mask_mode 2) the operand planes of the activated tensor instead of its fp32 copy."""
-    _chk(dA, 'dA')
+    shape, p, c, mptr = _flat_pc(dA, x, mask_src)
     x16 = x if isinstance(x, Act16) else None          # 16-bit-resident conv output (fp16 mode)
-    if x16 is not None:
-        assert prec == PREC_F16 and x16.lo is None and x16.inv is None
-        shape = x16.hi.shape
-    else:
-        _chk(x, 'x')
-        shape = x.shape
-    c = shape[-1]
-    p = dA.numel() // c
-    assert dA.shape == shape and c % 8 == 0, (dA.shape, shape)
+    assert c % 8 == 0 and (x16 is None or (prec == PREC_F16 and x16.lo is None and x16.inv is None)), (c, prec)
+    if isinstance(mask_src, Act16):                    # the ReLU pattern from the planes of the activated tensor (2 B per element)
+        assert mask_mode == 2, mask_mode
+        mask_mode = 3
     dev = dA.device
     hi = torch.empty(shape, dtype=torch.int16, device=dev)
     lo = torch.empty_like(hi) if prec == PREC_BF16X3 else None
@@ -1710,13 +1707,6 @@ def bn_bwd16(dA: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, s
     sc, dg, db = small[:2], small[2:2 + c], small[2 + c:]
     g = torch.empty(shape, dtype=torch.float32, device=dev) if want_g else None
     ws = torch.empty(_lib.lib().lp_bn_bwd16_workspace_bytes(p, c) // 4, dtype=torch.float32, device=dev)
-    mptr = None
-    if isinstance(mask_src, Act16):                    # the ReLU pattern from the planes of the activated tensor (2 B per element)
-        assert mask_mode == 2 and mask_src.hi.shape == shape, (mask_mode, mask_src.hi.shape, shape)
-        mask_mode, mptr = 3, mask_src.hi.data_ptr()
-    elif mask_src is not None:
-        _chk(mask_src, 'mask_src'); assert mask_src.shape == shape
-        mptr = mask_src.data_ptr()
     check(_lib.lib().lp_bn_bwd16_h(dA.data_ptr(), None if x16 is not None else x.data_ptr(), None if x16 is None else x16.hi.data_ptr(), mptr,
                                    gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), hi.data_ptr(), _p(lo),
                                    sc.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), p, c, mask_mode, float(act_hi), int(frozen), prec,

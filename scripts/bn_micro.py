@@ -1,7 +1,6 @@
 """Micro-benchmark of the BatchNorm-side kernels of the embedder on its own tensor shapes (ResNeXt-50 32x4d over 8 frames of 256 px:
 P pixels x C channels, NHWC fp32): lp_bn_bwd16 (partial + finalize + apply), lp_bn_train_stats, lp_norm_act_bwd, lp_act_pack (BN + ReLU
-prologue), lp_bn_add_act.  Prints us and GB/s of ALGORITHMIC bytes.  Knobs: LP_STAT_SPLIT_FIXED=1 (fixed 1024-pixel stage-1 split),
-LP_BNB_ITEMS=1 (one-item-per-thread apply), PREC."""
+prologue), lp_bn_add_act.  Prints us and GB/s of ALGORITHMIC bytes.  Knobs: LP_STAT_SPLIT_FIXED=1 (fixed 1024-pixel stage-1 split), PREC."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
