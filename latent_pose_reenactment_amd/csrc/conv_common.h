@@ -73,6 +73,7 @@ static inline void choose_tile(int BM, int N, int H, int W, int* lTH, int* lTW, 
 // conv_pipe.hip: the tap-pipelined 3x3 kernel.  -> 1: launched; 0: layer not covered (run conv_dma_kernel); < 0: error
 int lp_conv_pipe_launch(Conv16Params& p, int ups, int prec, hipStream_t s);
 int lp_conv1x1_pipe_launch(Conv16Params& p, int prec, hipStream_t s);      // the chunk-pipelined 1x1 kernel
+int lp_gconv_rows_launch(Conv16Params& p, int group_size, int prec, hipStream_t s);      // gconv_rows.hip: grouped 3x3, groups of 4 / 8 / 16
 
 // Epilogue of a conv workgroup.  acc[MR][NR]: the wave's (MR*16) x (NR*16) block in the MFMA 16x16 C layout (col = lane&15 = channel,
 // row = (lane>>4)*4 + reg = tile row); wave (wm, wn) of a WM x WN group whose tile starts at image n0, pixel (y0, x0), channel co0; `wave_d`

@@ -729,6 +729,12 @@ extern "C" int lp_gconv16_fwd_planes(const uint16_t* a_hi, const uint16_t* a_lo,
     p.stats = stats; p.stats_cap = stats ? stats_capacity_floats : 0; p.stats_rows = 0;
     hipStream_t s = (hipStream_t)stream;
     int rc;
+    // groups of 4 / 8 / 16 channels: the 16-channel-block kernel with register-resident weights (gconv_rows.hip; LP_GCONV_ROWS=0: this file's route)
+    rc = lp_gconv_rows_launch(p, group_size, prec, s);
+    if (rc) {
+        if (rc > 0 && stats_rows) *stats_rows = p.stats_rows;
+        return rc > 0 ? LP_OK : rc;
+    }
     // group_size (0: unknown) in 1 .. 32: the two 32-channel halves of a 64-channel block do not interact -- the kernel variant that skips
     // the zero half of every stage (LP_GCONV_HALF=0: the full block-diagonal product, the A/B baseline)
     static const bool half_env = !(getenv("LP_GCONV_HALF") && atoi(getenv("LP_GCONV_HALF")) == 0);

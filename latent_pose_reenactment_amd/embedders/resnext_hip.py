@@ -7,8 +7,10 @@ Data flow (NHWC fp32 activations, 16-bit operand planes for every contraction, a
            BatchNorm + ReLU + MaxPool(3,2,1) in one pass (lp_bn_relu_maxpool_fwd, 1-byte argmax for the backward)
   block    conv1 1x1 -> BN -> ReLU -> grouped 3x3 (stride 1|2) -> BN -> ReLU -> conv3 1x1 -> BN -> (+ identity | BN(downsample 1x1)) -> ReLU
            1x1 convs:   lp_conv16_fwd / lp_conv16_wgrad on the pixels flattened to one "image" (a 1x1 conv ignores the spatial structure)
-           grouped 3x3: lp_gconv16_fwd / lp_gconv16_wgrad (block-diagonal over aligned 64-channel blocks); stride 2 = full-resolution conv +
-                        lp_subsample2, its gradients through lp_zero_stuff2 (3 of the 16 blocks)
+           grouped 3x3: lp_gconv16_fwd / lp_gconv16_wgrad over aligned 64-channel blocks: forward and data gradient of the 4- / 8- / 16-channel
+                        groups (layers 1-3) on 16-channel MFMA blocks with register-resident weights (csrc/gconv_rows.hip), the 32-channel groups
+                        of layer 4 and the weight gradients in the block-diagonal form; stride 2 = full-resolution conv + lp_subsample2, its
+                        gradients through lp_zero_stuff2 (3 of the 16 blocks)
            BatchNorm:   train mode: lp_bn_train_stats (batch statistics + running-statistics update) -> per-channel (scale, shift) which
                         lp_act_pack (pro 4) applies with the ReLU while it writes the next conv's operand planes; the block output's
                         BN + residual + ReLU is lp_bn_add_act.  Backward: lp_norm_act_bwd (the AdaIN backward kernels with one "image").
