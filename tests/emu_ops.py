@@ -2,7 +2,8 @@
 path (embedders/resnext_hip.py, embedders/mobilenet_hip.py) is composed of.  TEST INFRASTRUCTURE ONLY:
   * on CPU it lets the orchestration (which kernel, on which tensor, in which order; what is saved for backward) be checked against
     the stock nn.Module autograd without a GPU: tests monkeypatch ``resnext_hip.ops`` with this module;
-  * on the GPU the same functions are the per-op references of tests/test_resnext_hip.py.
+  * on the GPU the same functions are the per-op references of tests/test_resnext_hip.py and, in fp64 on the CPU, of
+    tests/test_resident16_gpu.py (the last section: proven against autograd by tests/test_resident16_refs.py).
 "Operand planes" are ordinary float tensors here (``Act16.hi`` = the activated tensor itself), weight packs carry the weight and the
 orientation."""
 from typing import NamedTuple, Optional
@@ -271,3 +272,47 @@ def bn_bwd16(dA, x, gamma, mean, rstd, scale, shift, *, prec=0, mask_mode=0, mas
     dx, dg, db, g = norm_act_bwd(dA, x, gamma, mean, rstd, scale, shift, mask_mode=mask_mode, mask_src=mask_src, want_g=want_g, act_hi=act_hi,
                                  frozen=frozen)
     return Act16(dx, None, x.shape[-1], None), dg, db, g
+
+
+# ---- 16-bit-resident / planes-only kernels (tests/test_resident16_refs.py proves these on the CPU; tests/test_resident16_gpu.py uses them) ----
+def adain_relu_bwd(dA, x, add, gamma, mean, rstd, scale, shift, upsample):
+    """backward of relu(x * scale[n,c] + shift[n,c]) with per-image statistics [N,C] (+ x2 nearest upsample: dA [N,2H,2W,C] is first summed
+    over its 2x2 blocks); ``add`` (|None) is added to dx.  A per-image norm is a BatchNorm over one image: ``norm_act_bwd`` image by image.
+    -> (dx [N,H,W,C], dgamma [N,C], dbeta [N,C])"""
+    n, h, w, c = x.shape
+    if upsample:
+        dA = dA.reshape(n, h, 2, w, 2, c).sum(dim=(2, 4))
+    out = [norm_act_bwd(dA[i], x[i], gamma[i], mean[i], rstd[i], scale[i], shift[i])[:3] for i in range(n)]
+    dx, dgamma, dbeta = (torch.stack(t) for t in zip(*out))
+    return (dx if add is None else dx + add), dgamma, dbeta
+
+
+def plane_positive(bits):
+    """the kernels' "> 0" on a 16-bit operand element WITHOUT decoding it (norm_bwd.hip mask mode 3, lp_avgpool2_bwd_m16): sign clear and
+    magnitude non-zero, as one unsigned compare ((bits & 0xffff) - 1) mod 2^32 < 0x7fff.  Holds for fp16 and bf16 alike."""
+    b = bits.to(torch.int64) & 0xffff
+    return ((b - 1) & 0xffffffff) < 0x7fff
+
+
+def l1_planes(a, b):
+    """L1 between two taps given as the DECODED operand planes of relu(.) (a, b >= 0): -> (mean |a - b|, int8 sign pattern [numel]).
+    Pattern: +1 where a > b, -1 where a < b and a > 0, else 0 -- the forward's relu_in rule with the ReLU already applied (where the
+    plane of a is 0 the pre-activation was <= 0 and no gradient passes)."""
+    sgn = (a > b).to(torch.int8) - ((a < b) & (a > 0)).to(torch.int8)
+    return (a - b).abs().mean(), sgn.flatten()
+
+
+def avgpool2(x, relu_in, relu_out):
+    """AvgPool2d(2) of relu?(x) [N,2H,2W,C] -> [N,H,W,C]; relu_out: relu of the result"""
+    n, h2, w2, c = x.shape
+    v = torch.relu(x) if relu_in else x
+    y = v.reshape(n, h2 // 2, 2, w2 // 2, 2, c).sum(dim=(2, 4)) * 0.25
+    return torch.relu(y) if relu_out else y
+
+
+def avgpool2_bwd_mask(dy, mask):
+    """backward of AvgPool2d(2)(relu(x)): dx = 0.25 * dy[.., y >> 1, x >> 1, ..] * [mask > 0]; mask [N,2H,2W,C] = x or the decoded planes
+    of relu(x) (or the predicate itself as a bool tensor)"""
+    up = dy.repeat_interleave(2, 1).repeat_interleave(2, 2) * 0.25
+    m = mask if mask.dtype == torch.bool else mask > 0
+    return up * m
