@@ -495,6 +495,17 @@ int lp_image_prep_bwd(const float* g, const float* stdv, float* dx, int N, int H
  * LP_ERR_ARG: null pointer, N < 1, P or L outside 1 .. 256, parts outside 1 .. 16, S < 1, width <= 0 -- checked before any device work. */
 int lp_stickman_render(const float* points, int N, int P, const int* seg, const int* part_end, const float* colour, int L, int parts, int S,
                        float width, float* out, void* stream);
+/* (additive, ABI 12) Image-quality table of a batch (csrc/image_quality.hip holds the definition): x, y logical [B][C][H][W] fp32 read in place,
+ * stride_x / stride_y = 4 element strides (image, channel, row, column; HOST arrays read at call time); mask (|NULL) logical [B][H][W] fp32 with
+ * stride_m = 3 element strides (image, row, column; 0 allowed: an expanded view).  Both images are clamped to [0, 1]; the mask is used as given.
+ * out [B][6] fp32 = ssim (11-tap Gaussian window, sigma 1.5, valid positions only, C1 = 1e-4, C2 = 9e-4), psnr = -10 log10(max(mse, 1e-10)), l1,
+ * and the same three weighted by the mask (ssim_fg by the mask at the window centre): NaN without a mask or where the weight sum is 0.
+ * workspace: lp_image_quality_workspace_bytes(B, H, W) bytes of per-workgroup partial sums (no memset needed).  One launch plus a fixed-order finish
+ * launch, no atomics (bit-reproducible), no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer, B < 1, C outside 1 .. 4, H < 11 or W < 11 -- checked before any device work. */
+long long lp_image_quality_workspace_bytes(int B, int H, int W);
+int lp_image_quality(const float* x, const long long* stride_x, const float* y, const long long* stride_y, const float* mask,
+                     const long long* stride_m, int B, int C, int H, int W, float* workspace, float* out, void* stream);
 
 /* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per

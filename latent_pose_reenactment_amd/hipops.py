@@ -1178,6 +1178,55 @@ def stickman_render(points: Tensor, size: int, width: Optional[float] = None, ou
     return out
 
 
+IMAGE_QUALITY_COLUMNS = ('ssim', 'psnr', 'l1', 'ssim_fg', 'psnr_fg', 'l1_fg')
+
+
+def image_quality(x: Tensor, y: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """image-quality table [B, 6] (``IMAGE_QUALITY_COLUMNS``; fp32, on the device) of ``x`` [B, C, H, W] against ``y`` [B, C, H, W] or [B, K, C, H, W]
+    (its frame 0 is taken), both clamped to [0, 1]: SSIM (11-tap Gaussian window, valid positions), PSNR and L1 over the whole frame and weighted by
+    ``mask`` [B, H, W] (the ``_fg`` columns: NaN without a mask or where the weights sum to 0) -- the definition is the header comment of
+    csrc/image_quality.hip.  One launch plus its fixed-order finish launch on the current stream (lp_image_quality), bit-reproducible.  All three
+    tensors are read in place through their strides: a ``[:, 0]`` view of the images or an ``expand``ed mask is never materialised.  No gradient."""
+    for name, t in (('x', x), ('y', y)) + ((('mask', mask),) if mask is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'image_quality: {name} must be a tensor, got {type(t).__name__}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'image_quality: {name} must be fp32, got {t.dtype}')
+    if y.dim() == 5:
+        y = y[:, 0]
+    if x.dim() != 4 or y.dim() != 4:
+        raise ValueError(f'image_quality: expected x [B, C, H, W] and y [B, C, H, W] or [B, K, C, H, W], got {tuple(x.shape)} and {tuple(y.shape)}')
+    if x.shape != y.shape:
+        raise ValueError(f'image_quality: shape mismatch between x {tuple(x.shape)} and y {tuple(y.shape)}')
+    b, c, h, w = x.shape
+    if mask is not None and tuple(mask.shape) != (b, h, w):
+        raise ValueError(f'image_quality: shape mismatch between the mask {tuple(mask.shape)} and the images: expected {(b, h, w)}')
+    if b < 1 or c < 1:
+        raise ValueError(f'image_quality: empty batch {tuple(x.shape)}')
+    if h < 11 or w < 11:
+        raise ValueError(f'image_quality: H and W must be >= 11 (one 11 x 11 SSIM window), got {h} x {w}')
+    if c > 4:
+        raise ValueError(f'image_quality: at most 4 channels are supported, got C = {c}')
+    for name, t in (('x', x), ('y', y)) + ((('mask', mask),) if mask is not None else ()):
+        if not t.is_cuda or t.device != x.device:
+            raise ValueError(f'image_quality: {name} is on {t.device}: all inputs must be CUDA tensors on one device (the table is computed on the MI355X)')
+    import ctypes
+    x, y = x.detach(), y.detach()
+    sx, sy = (ctypes.c_longlong * 4)(*x.stride()), (ctypes.c_longlong * 4)(*y.stride())
+    sm = None
+    if mask is not None:
+        mask = mask.detach()
+        sm = (ctypes.c_longlong * 3)(*mask.stride())
+    l = _lib.lib()
+    work = torch.empty(l.lp_image_quality_workspace_bytes(b, h, w) // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty((b, 6), dtype=torch.float32, device=x.device)
+    npix = b * h * w
+    with _Timed('image_quality', 2.0 * 110 * c * npix, (b, h, w, c, 6, 11, 0, int(mask is not None)), (4 * npix * (2 * c + int(mask is not None)), 24 * b)):
+        check(l.lp_image_quality(x.data_ptr(), ctypes.addressof(sx), y.data_ptr(), ctypes.addressof(sy), _p(mask),
+                                 None if sm is None else ctypes.addressof(sm), b, c, h, w, work.data_ptr(), out.data_ptr(), _stream()), 'lp_image_quality')
+    return out
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)

@@ -4,7 +4,8 @@
   [all-reduce] -> step(D) -> EMA(0.999 | 0.972 when fine-tuning).
 The reference's apex ``Reducer`` is replaced by ``parallel.GradReducer`` (RCCL all-reduce over xGMI of exactly the
 gradients each optimizer is about to consume).  TensorBoard / image-grid logging branches (holycow.py:266-400) are
-observability and out of scope; scalar losses go to ``Meter`` as in the reference."""
+observability and out of scope; scalar losses go to ``Meter`` as in the reference, and so do the ``--metrics`` plugins' values
+(``Metric_<name>``, on the iterations whose losses are read back)."""
 import contextlib
 import copy
 import os
@@ -447,6 +448,12 @@ def run_epoch(dataloader, training_module, optimizer_G, optimizer_D, epoch, args
         if args.detailed_metrics and (not use_graph or it % log_every == 0):
             for name, value in itertools.chain(losses_G.items(), losses_D.items()):
                 meter.add(f'Loss_{name}', float(value))
+            if len(training_module.metric_list):
+                # ``--metrics``: on the iterations that sync anyway (the reference logs them as Metrics/<phase>/<name>).  With graph replay the
+                # metric launches run eagerly behind the replay, on the captured step's static outputs.
+                metrics = training_module.compute_metrics(all_data)
+                for name in metrics.keys():
+                    meter.add(f'Metric_{name}', metrics.get_average(name), metrics.get_num_measurements(name))
         if phase == 'train':
             # The reference advances args.iteration inside its TensorBoard branch, i.e. on the logging rank only (holycow.py:319,
             # 389-390) -- the rank that also names the checkpoints model_{iteration:08}.pth.  Logging is out of scope here, so the

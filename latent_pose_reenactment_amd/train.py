@@ -115,7 +115,9 @@ def main():
     if not args.weights_running_average:
         running_averages = None
     args.experiment_dir = Path(args.experiments_dir) / (args.experiment_name or 'run')
-    training_module = runner.TrainingModule(embedder, generator, discriminator, criterion_list, [], running_averages)
+    # metrics on the logging rank only, as in the reference (train.py:165-171)
+    metric_list = [metric.get_net(args) for metric in m['metric_list']] if args.logging and args.rank == 0 else []
+    training_module = runner.TrainingModule(embedder, generator, discriminator, criterion_list, metric_list, running_averages)
 
     saved = {'done': False}
     if args.rank == 0:
