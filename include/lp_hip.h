@@ -507,6 +507,19 @@ long long lp_image_quality_workspace_bytes(int B, int H, int W);
 int lp_image_quality(const float* x, const long long* stride_x, const float* y, const long long* stride_y, const float* mask,
                      const long long* stride_m, int B, int C, int H, int W, float* workspace, float* out, void* stream);
 
+/* (additive, ABI 12) Augmentation of the pose-encoder input (csrc/augment.hip holds the definition; the reference's augment_triplet,
+ * dataloaders/common/augmentation.py:123-142): pose, target logical [B][C][H][W] fp32, segm [B][Cs][H][W] fp32, all read in place; *_strides = 4
+ * element strides (image, channel, row, column; 0 allowed: an expanded view; HOST arrays read at call time).  target and segm are optional: each is
+ * given or omitted together with its strides and its output.  params [B][32] fp32, contiguous, DEVICE: per sample the 2 x 3 inverse maps of the
+ * pose image and of target / segm, the 3 x 3 filter of the pose image, mul, add[3], alpha, gain, sigma, seed (hipops.AUG_COLUMNS).
+ * pose_out / target_out [B][C][H][W], segm_out [B][Cs][H][W]: contiguous.  Bilinear resampling, reflect-101 border (segm: zero), then for the pose
+ * image the filter, multiply, add, linear and sigmoid contrast, hashed Gaussian noise and a clamp to [0, 1]; a neutral row copies bit for bit.
+ * ONE launch for the triplet, no atomics (bit-reproducible, independent of B), no workspace, no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer, B < 1, C or Cs outside 1 .. 4, H < 1 or W < 1 -- checked before any device work. */
+int lp_augment_triplet(const float* pose, const long long* pose_strides, const float* target, const long long* target_strides,
+                       const float* segm, const long long* segm_strides, const float* params, int B, int C, int Cs, int H, int W,
+                       float* pose_out, float* target_out, float* segm_out, void* stream);
+
 /* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.

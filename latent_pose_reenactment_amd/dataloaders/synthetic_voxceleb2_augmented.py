@@ -1,0 +1,39 @@
+"""``synthetic_voxceleb2`` plus the reference's augmentation flags (dataloaders/voxceleb2_segmentation_nolandmarks.py:243-246 calls
+``augmenter.augment_triplet`` on every training sample): the images are the base loader's, bit for bit; when ``--use_pixelwise_augs``,
+``--use_affine_scale`` or ``--use_affine_shift`` is on, every sample also carries
+  data_dict:   ... + aug_params 32 floats (hipops.AUG_COLUMNS): what the augmenter drew for this sample
+and the pixels are augmented on the device at the top of the training forward (augmentation.apply).  The draw is seeded from (seed, index, how often
+this index has been served) for ``part == 'train'`` -- every visit of a sample sees another augmentation -- and from (seed, index) alone otherwise:
+the reference's ``deterministic_`` for validation.  With all three flags off (or ``--inference``) no ``aug_params`` is emitted."""
+import torch
+
+from latent_pose_reenactment_amd import augmentation
+from latent_pose_reenactment_amd.dataloaders import synthetic_voxceleb2 as _base
+
+
+class Dataset(_base.Dataset):
+    @staticmethod
+    def get_args(parser):
+        _base.Dataset.get_args(parser)
+        return augmentation.get_args(parser)
+
+    @staticmethod
+    def get_dataset(args, part):
+        return Dataset(args, part)
+
+    def __init__(self, args, part):
+        super().__init__(args, part)
+        self.augmenter = augmentation.ParametricAugmenter(args)
+        self.part = part
+        self.visits = {}
+
+    def __getitem__(self, index):
+        data, target = _base.make_sample(index, self.size, self.frames, self.num_labels, self.finetune, self.seed)
+        if not self.augmenter.is_empty():
+            visit = 0
+            if self.part == 'train':
+                visit = self.visits.get(index, 0)
+                self.visits[index] = visit + 1
+            g = torch.Generator().manual_seed((self.seed * 1000003 + index) * 8191 + visit + 700001)     # (its own stream, as the keypoints have)
+            data['aug_params'] = self.augmenter.sample(g)
+        return data, target

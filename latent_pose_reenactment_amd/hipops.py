@@ -1227,6 +1227,75 @@ def image_quality(x: Tensor, y: Tensor, mask: Optional[Tensor] = None) -> Tensor
     return out
 
 
+AUG_COLUMNS = ('pose_a00', 'pose_a01', 'pose_a02', 'pose_a10', 'pose_a11', 'pose_a12',
+               'target_a00', 'target_a01', 'target_a02', 'target_a10', 'target_a11', 'target_a12',
+               'k00', 'k01', 'k02', 'k10', 'k11', 'k12', 'k20', 'k21', 'k22',
+               'mul', 'add_r', 'add_g', 'add_b', 'alpha', 'gain', 'sigma', 'seed', 'reserved0', 'reserved1', 'reserved2')
+
+
+def _aug_frame(name: str, t: Tensor):
+    """[B, C, H, W] or [B, 1, C, H, W] -> (the 4-D view, was it 5-D)"""
+    if t.dim() == 5 and t.shape[1] == 1:
+        return t[:, 0], True
+    if t.dim() != 4:
+        raise ValueError(f'augment_triplet: {name} must be [B, C, H, W] or [B, 1, C, H, W], got shape {tuple(t.shape)}')
+    return t, False
+
+
+def augment_triplet(pose: Tensor, params: Tensor, target: Optional[Tensor] = None, segm: Optional[Tensor] = None):
+    """(pose', target', segm') of the augmentation defined in the header comment of csrc/augment.hip: ``params`` [B, 32] (``AUG_COLUMNS``) holds per
+    sample the inverse affine maps, the 3 x 3 filter and the pixelwise parameters.  ``pose`` / ``target``: [B, C, H, W] or [B, 1, C, H, W] of one
+    shape, ``segm``: the same with its own channel count (at most 4 channels each); every result has its input's shape, an absent input gives None.
+    ONE launch on the current stream (lp_augment_triplet), bit-reproducible; the inputs are read in place through their strides -- a ``[:, 0]``
+    view or an ``expand``ed mask is never materialised.  No gradient."""
+    given = [('pose', pose), ('params', params)] + ([('target', target)] if target is not None else []) + ([('segm', segm)] if segm is not None else [])
+    for name, t in given:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'augment_triplet: {name} must be a tensor, got {type(t).__name__}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'augment_triplet: {name} must be fp32, got {t.dtype}')
+    p4, p5 = _aug_frame('pose', pose)
+    b, c, h, w = p4.shape
+    t4 = s4 = None
+    if target is not None:
+        t4, t5 = _aug_frame('target', target)
+        if t4.shape != p4.shape:
+            raise ValueError(f'augment_triplet: shape mismatch between pose {tuple(pose.shape)} and target {tuple(target.shape)}')
+    if segm is not None:
+        s4, s5 = _aug_frame('segm', segm)
+        if (s4.shape[0], s4.shape[2], s4.shape[3]) != (b, h, w):
+            raise ValueError(f'augment_triplet: shape mismatch between pose {tuple(pose.shape)} and segm {tuple(segm.shape)}')
+    if tuple(params.shape) != (b, len(AUG_COLUMNS)):
+        raise ValueError(f'augment_triplet: params must be [B, 32] = {(b, len(AUG_COLUMNS))}, got {tuple(params.shape)}')
+    if b < 1 or c < 1 or h < 1 or w < 1 or (s4 is not None and s4.shape[1] < 1):
+        raise ValueError(f'augment_triplet: empty input {tuple(pose.shape)}')
+    if c > 4 or (s4 is not None and s4.shape[1] > 4):
+        raise ValueError(f'augment_triplet: at most 4 channels are supported, got C = {c}' + ('' if s4 is None else f', Cs = {s4.shape[1]}'))
+    for name, t in given:
+        if not t.is_cuda:
+            raise ValueError(f'augment_triplet: {name} is on {t.device}: all inputs must be CUDA tensors (the host version is '
+                             'augmentation.augment_triplet_host)')
+        if t.device != pose.device:
+            raise ValueError(f'augment_triplet: mixed devices: {name} is on {t.device}, pose on {pose.device}')
+    import ctypes
+    cs = 1 if s4 is None else s4.shape[1]
+    par = params.detach().contiguous()
+    srcs = [t if t is None else t.detach() for t in (p4, t4, s4)]
+    strides = [None if t is None else (ctypes.c_longlong * 4)(*t.stride()) for t in srcs]
+    outs = [None if t is None else torch.empty(t.shape, dtype=torch.float32, device=pose.device) for t in srcs]
+    npix = b * h * w
+    chans = c * (1 + int(t4 is not None)) + (cs if s4 is not None else 0)
+    with _Timed('augment', 2.0 * npix * (9 * c + 8 * chans), (b, h, w, c, cs, 3, int(t4 is not None), int(s4 is not None)),
+                (4 * npix * chans + 128 * b, 4 * npix * chans)):
+        check(_lib.lib().lp_augment_triplet(_p(srcs[0]), ctypes.addressof(strides[0]),
+                                            _p(srcs[1]), None if strides[1] is None else ctypes.addressof(strides[1]),
+                                            _p(srcs[2]), None if strides[2] is None else ctypes.addressof(strides[2]),
+                                            par.data_ptr(), b, c, cs, h, w, _p(outs[0]), _p(outs[1]), _p(outs[2]), _stream()), 'lp_augment_triplet')
+    return (outs[0].unsqueeze(1) if p5 else outs[0],
+            None if t4 is None else (outs[1].unsqueeze(1) if t5 else outs[1]),
+            None if s4 is None else (outs[2].unsqueeze(1) if s5 else outs[2]))
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)
