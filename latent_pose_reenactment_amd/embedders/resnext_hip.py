@@ -27,7 +27,7 @@ import torch
 
 from latent_pose_reenactment_amd import hipops as ops
 from latent_pose_reenactment_amd import streams as _streams
-from latent_pose_reenactment_amd._lib import PREC_BF16, PREC_BF16X3, PREC_F16
+from latent_pose_reenactment_amd._lib import PREC_BF16X3, PREC_F16
 
 
 class _BN:
@@ -46,7 +46,7 @@ def supported(n: int, h: int, w: int) -> bool:
 
 
 Y16 = os.environ.get('LP_E_Y16', '1') != '0'        # fp16 mode: conv outputs stay 16-bit resident
-RES16 = os.environ.get('LP_E_RES16', '1') != '0'    # identity shortcuts of bf16 / bf16x3 blocks read the block input from its operand planes; no fp32 block output there
+RES16 = os.environ.get('LP_E_RES16', '1') != '0'    # identity shortcuts of bf16x3 blocks read the block input from its operand planes (hi + lo); no fp32 block output there
 MASK16 = os.environ.get('LP_E_MASK16', '1') != '0'  # block-output ReLU pattern from the operand planes in every mode (0: from the fp32 copy outside the fp16 mode)
 
 
@@ -141,8 +141,9 @@ class ResNeXtFunction(torch.autograd.Function):
 
         def next_prec(b):          # mode of the planes block b writes for its consumer
             return lprecs[(net._hip_blocks[b + 1][0], 'conv1')] if b + 1 < nblk else bprecs[b]
-        # identity shortcuts read from the operand planes of the block input (RES16): blocks whose input and output planes share a bf16-class mode
-        planes_res = [RES16 and MASK16 and not blk[5] and lprecs[(blk[0], 'conv1')] in (PREC_BF16, PREC_BF16X3) and next_prec(b) == lprecs[(blk[0], 'conv1')]
+        # identity shortcuts read from the operand planes of the block input (RES16): blocks whose input and output planes are both bf16x3 -- hi + lo
+        # carry 16 significant bits; plain bf16 planes (8) are no more a residual stream than fp16 ones (11): those blocks add the fp32 block input
+        planes_res = [RES16 and MASK16 and not blk[5] and lprecs[(blk[0], 'conv1')] == PREC_BF16X3 and next_prec(b) == PREC_BF16X3
                       for b, blk in enumerate(net._hip_blocks)]
         for bi, (bname, cin, width, cout, stride, down) in enumerate(net._hip_blocks):
             prec = bprecs[bi]

@@ -55,6 +55,110 @@ def test_resnext_function_matches_stock_autograd(monkeypatch, train, mode):
         assert rel(b2, b1) < 1e-10, k
 
 
+# every operand-mode assignment the encoder can run under: tests/rounding_study.py CASES (the three uniform modes; the default assignment
+# -- LP_PREC, LP_PREC_E, LP_E_HEAD_F16 unset -- with an fp16 tail of 0 .. 6 of the 6 bottlenecks: whether a downsample or an identity
+# block sits in front of the tail decides which route writes the planes the tail reads; layer kinds of the head moved to fp16; each of
+# the three route switches off)
+MODE_CASES = ['bf16x3', 'f16', 'bf16', 'tail0', 'tail1', 'tail2', 'tail3', 'tail4', 'tail6',
+              'tail2-head-conv2', 'tail2-head-conv1,conv3', 'tail2-head-conv1,conv2,conv3',
+              'tail2-RES16=0', 'tail2-MASK16=0', 'tail2-Y16=0', 'tail3-RES16=0', 'tail3-MASK16=0', 'tail3-Y16=0', 'f16-Y16=0']
+
+
+@pytest.mark.parametrize('case', MODE_CASES)
+@pytest.mark.parametrize('train', [True, False])
+def test_resnext_function_under_every_mode_assignment(monkeypatch, train, case):
+    """the orchestration under every assignment of operand modes, through the MODE-AWARE emulation (tests/emu_modes.py): the stock-layer
+    result to rounding as above, and every operand plane and weight pack reaches its consumer in the mode it was written in (the layer
+    raises otherwise: on the GPU the planes carry no mode and would be read as the wrong number format), a 16-bit-resident conv output
+    is fp16, and only bf16x3 blocks take the planes-residual route"""
+    import emu_modes
+    import rounding_study as RS
+    from embedders import resnext_hip
+    RS.select(monkeypatch, case)
+    RS.install(monkeypatch, emu_modes)
+    m = RS.make_net(16, 3, (2, 2, 1, 1)).double()
+    m2 = copy.deepcopy(m)
+    m.train(train); m2.train(train)
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(8, 3, 64, 64, dtype=torch.double, generator=g)
+    r = torch.randn(8, 16, dtype=torch.double, generator=g)
+    y_ref = BR.resnext_forward(m, x)
+    (y_ref * r).sum().backward()
+    m2._hip_structure()
+    emu_modes.reset()
+    try:
+        y = resnext_hip.ResNeXtFunction.apply(m2, x, *[p for _, p in m2.named_parameters()])
+        (y * r).sum().backward()
+        assert emu_modes.checks[0] > 100, emu_modes.checks[0]          # (6 bottlenecks: > 30 contractions forward, twice that backward, 2 operands each)
+    finally:
+        emu_modes.reset()
+    assert rel(y, y_ref) < 1e-10
+    for (k, p1), (_, p2) in zip(m.named_parameters(), m2.named_parameters()):
+        assert p2.grad is not None and rel(p2.grad, p1.grad) < 1e-9, k
+    for (k, b1), (_, b2) in zip(m.named_buffers(), m2.named_buffers()):
+        assert rel(b2, b1) < 1e-10, k
+
+
+def test_mode_aware_emulation_raises_on_a_mismatch():
+    """the layer cannot go quietly inert: a plane tagged in one mode and handed to a contraction in another raises and names the consumer;
+    likewise a wrong pack, an untagged plane, a bf16 planes residual and a y16 plane that is not fp16"""
+    import emu_modes as M
+    M.reset()
+    try:
+        x = torch.rand(1, 4, 4, 8, dtype=torch.double)
+        w = torch.rand(16, 8, 1, 1, dtype=torch.double)
+        a = M.act_pack(x, pro=0, prec=M.BF16X3)
+        pack = M.PackBatch([(w, 0, False)], M.F16).update()[0]
+        with pytest.raises(M.ModeError, match=r'conv16 \(conv1x1, forward pack\): the activation plane was written as bf16x3 and is consumed as f16'):
+            M.conv16(a, pack, ksize=1, prec=M.F16, kind='conv1x1')
+        with pytest.raises(M.ModeError, match='the weight pack was written as f16 and is consumed as bf16x3'):
+            M.conv16(M.flat16(a), pack, ksize=1, prec=M.BF16X3)          # (the tag survives the flattened view)
+        y = M.conv16(M.act_pack(x, pro=0, prec=M.F16), pack, ksize=1, prec=M.F16)
+        assert y.shape == (1, 4, 4, 16)
+        with pytest.raises(M.ModeError, match='untagged'):
+            M.conv16(M.Act16(x.clone(), None, 8, None), pack, ksize=1, prec=M.F16)
+        with pytest.raises(M.ModeError, match='gradient plane was written as bf16 '):
+            M.conv_wgrad16(a, M.act_pack(y, prec=M.BF16, grad=True), ksize=1, prec=M.BF16X3)
+        sc = torch.ones(8, dtype=torch.double)
+        with pytest.raises(M.ModeError, match='bf16 block takes the planes-residual route'):
+            M.bn_add_act(x, sc, sc, M.act_pack(x, pro=0, prec=M.BF16), relu=True, prec=M.BF16)
+        with pytest.raises(M.ModeError, match='residual plane was written as bf16x3 and is consumed as f16'):
+            M.bn_add_act(x, sc, sc, a, relu=True, prec=M.F16)
+        with pytest.raises(M.ModeError, match='16-bit-resident conv output was written as bf16x3'):
+            M.bn_act16(a, sc, sc)
+        with pytest.raises(M.ModeError, match='lp_bn_add_act16 writes fp16 planes only'):
+            M.bn_add_act(M.act_pack(x, pro=0, prec=M.F16), sc, sc, x, relu=True, prec=M.BF16X3)
+        assert M.mode_of(M.subsample2_16(a)) == M.BF16X3 and M.mode_of(M.zero_stuff2_16(a, 8, 8)) == M.BF16X3
+    finally:
+        M.reset()
+
+
+def test_rounding_emulation_orders_the_modes():
+    """the rounding form of the layer (what the gates of tests/test_resnext_hip.py are derived from): off, it is exact; on, the error follows
+    the operand formats -- bf16x3 (2^-17) < f16 (2^-12) < bf16 (2^-9), the default assignment (bf16x3 head, fp16 tail) above bf16x3 and below bf16"""
+    import rounding_study as RS
+    e = {c: RS.predict(c, False, num_classes=16, frames=(8, 64, 3)) for c in ('bf16x3', 'tail2', 'f16', 'bf16')}
+    for k in ('logits', 'grads'):
+        assert 0 < e['bf16x3'][k] < e['f16'][k] < e['bf16'][k] and e['bf16x3'][k] < e['tail2'][k] < e['bf16'][k], (k, e)
+    assert e['bf16x3']['logits'] < 2.0 ** -12 and e['bf16']['logits'] > 2.0 ** -12, e
+
+
+def _gpu_mode_predictions():
+    import test_resnext_hip
+    return sorted(c for c, train in test_resnext_hip.MODE_PREDICTIONS if not train)
+
+
+@pytest.mark.parametrize('case', _gpu_mode_predictions())
+def test_gpu_gates_are_what_the_rounding_emulation_predicts(case):
+    """the MODE_PREDICTIONS table of tests/test_resnext_hip.py (its gates are 3x these) against the helper it was taken from: eval mode, where
+    the figure does not depend on summation order (the table holds 3 digits: 2 %)"""
+    import rounding_study as RS
+    import test_resnext_hip
+    e = RS.predict(case, False)
+    p_out, p_tot, p_b = test_resnext_hip.MODE_PREDICTIONS[(case, False)]
+    assert abs(e['logits'] - p_out) <= 0.02 * p_out and abs(e['grads'] - p_tot) <= 0.02 * p_tot and e['buffers'] == p_b == 0.0, (e, p_out, p_tot, p_b)
+
+
 @pytest.mark.parametrize('train', [True, False])
 def test_mobilenet_training_path_matches_stock_autograd(monkeypatch, train):
     """MobileNetV2 with autograd on (embedders/mobilenet_hip.py): features Function + Dropout + classifier Function vs the stock

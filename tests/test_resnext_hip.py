@@ -465,6 +465,89 @@ def test_resnext_forward_backward_vs_fp64(monkeypatch, prec_name, train, depth):
             assert int(b) == int(q), k
 
 
+# predicted (logits, all gradients, worst BatchNorm buffer) of each assignment (tests/rounding_study.py CASES) on _nets(32, 7, (2, 2, 1, 1)) and
+# structured_frames(8, 128, 3): tests/rounding_study.py predict() -- the orchestration through the mode-aware emulation in fp64 with the operands
+# of every contraction rounded according to the ``prec`` that call receives (bf16: one bf16; bf16x3: hi + lo; f16: fp16, gradient operands
+# with their power-of-two scale), 16-bit-resident conv outputs rounded to fp16, fp32 results to fp32; no kernel involved
+# (``python scripts/embedder_rounding_study.py CASE`` prints a row).  The gates are 3x these figures.  Eval mode leaves the buffers alone: 0.
+MODE_PREDICTIONS = {
+    ('bf16', False): (4.18e-03, 6.30e-03, 0.0), ('bf16', True): (3.00e-02, 4.82e-01, 3.68e-03),
+    ('tail1', False): (1.73e-04, 1.28e-03, 0.0), ('tail1', True): (2.35e-04, 3.22e-02, 1.32e-04),
+    ('tail2', False): (2.78e-04, 1.79e-03, 0.0), ('tail2', True): (4.79e-04, 4.98e-02, 1.53e-04),
+    ('tail3', False): (2.72e-04, 2.24e-03, 0.0), ('tail3', True): (6.61e-04, 6.07e-02, 1.53e-04),
+    ('tail2-head-conv2', False): (2.93e-04, 1.86e-03, 0.0), ('tail2-head-conv2', True): (1.23e-03, 8.58e-02, 1.71e-04),
+    ('tail2-head-conv1,conv3', False): (2.90e-04, 1.78e-03, 0.0), ('tail2-head-conv1,conv3', True): (1.90e-03, 1.20e-01, 2.32e-04),
+    ('tail2-RES16=0', False): (2.78e-04, 1.79e-03, 0.0), ('tail2-RES16=0', True): (4.75e-04, 4.57e-02, 1.53e-04),
+    ('tail2-MASK16=0', False): (2.78e-04, 1.79e-03, 0.0), ('tail2-MASK16=0', True): (4.75e-04, 4.57e-02, 1.53e-04),
+    ('tail2-Y16=0', False): (2.78e-04, 1.73e-03, 0.0), ('tail2-Y16=0', True): (4.25e-04, 4.07e-02, 1.53e-04),
+}
+
+
+@pytest.mark.parametrize('train', [True, False])
+@pytest.mark.parametrize('case', sorted(set(c for c, _ in MODE_PREDICTIONS)))
+def test_resnext_operand_mode_assignments_vs_fp64(monkeypatch, case, train):
+    """the assignments of operand modes that no uniform LP_PREC_E run reaches -- plain bf16; the default bf16x3 head + fp16 tail with the tail
+    starting behind a downsample block (1, 3) and behind an identity block (2); layer kinds of the head moved to fp16; each route switch
+    (planes residual, ReLU pattern from the hi plane, 16-bit-resident conv outputs) off -- on a shallow net with two identity blocks at the
+    smallest geometry the path admits: logits, EVERY parameter gradient and the BatchNorm buffers against the stock layers in fp64 (same
+    device), each within 3x what the operand rounding of that assignment predicts (MODE_PREDICTIONS).  A plane or pack that reaches a
+    contraction in another mode than it was written in is read as the wrong number format: an error of order 1, not of 3x."""
+    import rounding_study as RS
+    from oracle import backbones_ref as BR
+    RS.select(monkeypatch, case)
+    m, ref = _nets(32, 7, (2, 2, 1, 1))
+    m32 = copy.deepcopy(m)
+    for net in (m, ref, m32):
+        net.train(train)
+    x = structured_frames(8, 128, 3).cuda()
+    r = RS.loss_weights(8, 32).cuda()
+    y = m(x)
+    assert m.__dict__.get('_hip_param_names') is not None, 'the HIP path did not run'
+    (y * r).sum().backward()
+    yr = BR.resnext_forward(ref, x.double())
+    (yr * r.double()).sum().backward()
+    y32 = BR.resnext_forward(m32, x)
+    (y32 * r).sum().backward()
+    e, c = RS.errors(m, ref, y, yr), RS.errors(m32, ref, y32, yr)
+    p_out, p_tot, p_b = MODE_PREDICTIONS[(case, train)]
+    print(f'[parity] [2,2,1,1] {case} train={train} 128px: logits {e["logits"]:.2e} (predicted {p_out:.2e}), all-gradients {e["grads"]:.2e} '
+          f'(predicted {p_tot:.2e}; cosine {_cos(list(m.parameters()), list(ref.parameters())):.4f}), buffers {e["buffers"]:.2e} (predicted {p_b:.2e}) '
+          f'| stock fp32 layers vs fp64: logits {c["logits"]:.2e}, all-gradients {c["grads"]:.2e}, buffers {c["buffers"]:.2e}')
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in m.parameters())
+    assert e['logits'] <= 3 * p_out and e['grads'] <= 3 * p_tot and e['buffers'] <= 3 * p_b, (e, c)
+    for (k, b), (_, q) in zip(m.named_buffers(), ref.named_buffers()):
+        if not b.dtype.is_floating_point:
+            assert int(b) == int(q), k
+
+
+@pytest.mark.parametrize('case', ['bf16x3', 'tail2'])
+def test_relu_pattern_source_changes_no_result(monkeypatch, case):
+    """with the fp32 residual in both runs (RES16 off), MASK16 on and off run the SAME forward and differ only in where the backward reads the
+    block-output ReLU pattern (hi plane | fp32 copy), and out > 0 <=> its 16-bit rounding > 0: bit-equal logits, and gradients that differ
+    by no more than two runs of the MASK16-on configuration differ from each other (bit-equal if that route is deterministic)"""
+    import rounding_study as RS
+
+    def run(name):
+        with pytest.MonkeyPatch.context() as mp:
+            RS.select(mp, name)
+            m, _ = _nets(32, 7, (2, 2, 1, 1))
+            m.train()
+            y = m(structured_frames(8, 128, 3).cuda())
+            (y * RS.loss_weights(8, 32).cuda()).sum().backward()
+            return y.detach(), [p.grad for p in m.parameters()]
+
+    def diff(ga, gb):
+        return max(float((a - b).abs().max()) for a, b in zip(ga, gb))
+    y_a, g_a = run(case + '-RES16=0')
+    y_b, g_b = run(case + '-RES16=0')
+    y_c, g_c = run(case + '-RES16=0-MASK16=0')
+    assert torch.equal(y_a, y_b) and torch.equal(y_a, y_c)
+    noise, d = diff(g_a, g_b), diff(g_a, g_c)
+    print(f'[parity] [2,2,1,1] {case}, fp32 residual: ReLU pattern from the hi plane vs from the fp32 copy: max |gradient difference| {d:.3e} '
+          f'(two runs of the hi-plane route: {noise:.3e})')
+    assert d <= noise, (d, noise)
+
+
 def test_embedder_plugin_uses_hip_identity_encoder(monkeypatch):
     """the plugin call site (get_identity_embedding: B x K frames -> embeds) reaches the HIP function, and the frame mean is differentiable"""
     import argparse
