@@ -520,6 +520,20 @@ int lp_augment_triplet(const float* pose, const long long* pose_strides, const f
                        const float* segm, const long long* segm_strides, const float* params, int B, int C, int Cs, int H, int W,
                        float* pose_out, float* target_out, float* segm_out, void* stream);
 
+/* (additive, ABI 12) From decoded frames to network-ready tensors (csrc/frames.hip holds the definition; the reference's SampleLoader.load_sample,
+ * dataloaders/voxceleb2_segmentation_nolandmarks.py:89-175): buf = buf_bytes uint8 on the DEVICE, the decoded frames of a batch packed back to
+ * back; the table = rows x 24 int64 (frames.COLUMNS), given twice: table_host is read and checked at call time, table_dev is the same table on the
+ * DEVICE.  A row holds an image view (offset, H, W, row stride, pixel stride), its box (t, l, b, r; b, r exclusive, square) and mode (0 area when
+ * S <= n, 1 cubic), the same for a one-channel mask view, and the slots of its outputs (-1: absent): image [n_image][3][S][S], mask
+ * [n_mask][3][S][S] (the one mask value in 3 planes), product [n_product][3][S][S] = image x mask; fp32, contiguous; every slot below its count
+ * must be written by exactly one row (not checked here).  Crop through the border rule (image: reflect-101, mask: 0 above, replicate elsewhere),
+ * separable area / cubic (A = -0.75) / linear resampling to S x S in fp32, / 255; a row with n == S gives exactly v / 255.
+ * ONE launch, no atomics (bit-reproducible, independent of the other rows), no workspace, no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG (naming the row): null pointer, rows outside 1 .. 65535, S outside 1 .. 4096, a slot outside its count, a box that is not square, a
+ * view outside buf, a mode the sizes do not give; LP_ERR_UNSUPPORTED: a crop above 8 S -- all checked before any device work. */
+int lp_frames_prepare(const unsigned char* buf, long long buf_bytes, const long long* table_host, const long long* table_dev, int rows, int S,
+                      float* image, int n_image, float* mask, int n_mask, float* product, int n_product, void* stream);
+
 /* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.

@@ -1,8 +1,10 @@
 """Dataloader front-end with the reference's surface (dataloaders/dataloader.py:10-50): ``Dataloader(name)`` resolves
 ``dataloaders.<name>.Dataset``, adds ``--num_workers/--prefetch_size/--batch_size`` and builds a loader whose per-GPU
 batch is ``batch_size // num_gpus`` over a rank-strided subset.  The reference's prefetching subclass pokes torch-1.5
-private iterator classes and its VoxCeleb2 datasets need cv2/imgaug/pandas: host-side I/O, out of scope here
- -- only the output contract matters, which ``synthetic_voxceleb2`` reproduces."""
+private iterator classes and is not reproduced (dataloaders/prefetch.py is the input side here).  A plugin may bring its
+own loader through ``Dataset.get_dataloader(args, part)``: ``voxceleb2_segmentation_nolandmarks`` does, to decode image
+folders in workers and make the batch on the device (frames.py); ``synthetic_voxceleb2`` gives the same output contract
+without a dataset."""
 import logging
 
 import torch

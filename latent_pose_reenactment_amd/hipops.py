@@ -1296,6 +1296,28 @@ def augment_triplet(pose: Tensor, params: Tensor, target: Optional[Tensor] = Non
             None if s4 is None else (outs[2].unsqueeze(1) if s5 else outs[2]))
 
 
+def frames_prepare(buf: Tensor, table: Tensor, size: int):
+    """(image, mask, product) of the frame preparation defined in the header comment of csrc/frames.hip: ``buf`` = the decoded uint8 frames of a
+    batch, packed, on the device; ``table`` = int64 [R, 24] (``frames.COLUMNS``) on the HOST, one row per output image: an image view with its box
+    and mode, a mask view with its box, and the slot of each output.  Every result is fp32 [slots, 3, size, size], None where no row asks for it.
+    The table is checked here (ValueError naming the row: a box that is not square, a view outside ``buf``, a scale above 8) and copied to the
+    device; then ONE launch on the current stream (lp_frames_prepare), bit-reproducible.  No gradient."""
+    from latent_pose_reenactment_amd import frames
+    if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.dim() == 1):
+        raise ValueError('frames_prepare: buf must be a 1-D uint8 tensor')
+    if not buf.is_cuda:
+        raise ValueError(f'frames_prepare: buf is on {buf.device}: it must be a CUDA tensor (the host version is frames.prepare_host)')
+    size = int(size)
+    counts = frames.check_table(table, buf.numel(), size)
+    buf, table = buf.contiguous(), table.contiguous()
+    with torch.cuda.device(buf.device):
+        table_dev = (table if table.is_pinned() else table.pin_memory()).to(buf.device, non_blocking=True)
+        outs = [torch.empty((c, 3, size, size), dtype=torch.float32, device=buf.device) if c else None for c in counts]
+        check(_lib.lib().lp_frames_prepare(buf.data_ptr(), buf.numel(), table.data_ptr(), table_dev.data_ptr(), table.shape[0], size,
+                                           _p(outs[0]), counts[0], _p(outs[1]), counts[1], _p(outs[2]), counts[2], _stream()), 'lp_frames_prepare')
+    return tuple(outs)
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)
