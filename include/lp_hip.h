@@ -37,6 +37,13 @@ int lp_abi_version(void);
  *   (y + a - 1 + i, x + b - 1 + j); the taps that meet the same pixel are summed in fp32 before the 16-bit split.
  *   mode 2 (forward): out[t][co][ci];  mode 3 (data gradient): out[t][ci][co] = the (phase, 1 - i, 1 - j) sums.
  *   Consumed by lp_conv16_fwd(_stats) with upsample = 2 (forward) / 3 (data gradient): 4/9 of the matrix work of the fused-upsample conv.
+ * modes 4 / 5 (T = 9 in, sixteen taps out): a 3x3 conv FOLLOWED BY nn.AvgPool2d(2) (the critic's down blocks, generators/common/blocks.py:76-90) as one 4x4
+ *   stride-2 conv: pooled[y] = sum_{u = -1..2} W4[u] in[2y + u] with W4[u] = 1/4 * the sum of w[dy] over dy = u - a + 1 in [0, 2], a in {0, 1} (rows;
+ *   columns alike), summed in fp32 before the 16-bit split.
+ *   mode 4 (forward): out[t = pa * 8 + pb * 4 + ky * 2 + kx][co][ci] = W4[2 ky - pa][2 kx - pb]   (lp_conv16_fwd upsample = 3, the gather form);
+ *   mode 5 (data gradient): out[t = a * 8 + b * 4 + i * 2 + j][ci][co] = W4[u_a(i)][u_b(j)], u_0 = (2, 0), u_1 = (1, -1): hi-res pixel (2y + a, 2x + b)
+ *   collects from the pooled pixel (y + a - 1 + i, x + b - 1 + j)   (lp_conv16_fwd upsample = 2).
+ * Every mode >= 2 needs T = 9 (LP_ERR_ARG otherwise).  Pad rows and columns are zero words in every mode.
  * f16 = 0: hi = bf16(w), lo = bf16(w - hi) (may be NULL);  f16 = 1: hi = fp16(w) (saturating), lo unused.
  * Replaces nothing in the reference (cuDNN does this internally). */
 int lp_pack_weights(const float* w, uint16_t* hi, uint16_t* lo, int Cout, int Cin, int T, int RowsP, int ColsP, int mode, int f16,
@@ -57,7 +64,8 @@ int lp_pack_weights_pairs(const void* table, int num_entries, long long total_ti
 /* Operand planes of a conv input: hi (, lo) [N*HW][C8] 16-bit, C8 = C rounded up to 8 (pad channels zero), holding
  *   act(x) * in_scale,  act: pro 0 identity | 1 relu(x*scale[n,c]+shift[n,c]) | 2 relu(x) | 3 relu6(x*scale[c]+shift[c]) |
  *                            4 relu(x*scale[c]+shift[c]) | 5 x*scale[c]+shift[c]   (3..5: BatchNorm folded to a per-channel affine)
- * in the operand format of `prec` (bf16 | bf16 hi+lo | fp16, saturating).  Replaces, once per tensor, the instance_norm + mul +
+ * in the operand format of `prec` (bf16 | bf16 hi+lo | fp16, saturating: +-inf and everything beyond +-65504 become +-65504; the bf16 modes keep +-inf).
+ * A NaN stays NaN in every mode and through every prologue (a ReLU does not mask it); the lo word of an infinite bf16 hi+lo operand is NaN (inf - inf).  Replaces, once per tensor, the instance_norm + mul +
  * add + relu chain of AdaptiveNorm2d/ReLU (generators/common/blocks.py:18-26,70-73) that the reference runs before every conv;
  * the planes feed lp_conv16_fwd (forward / dgrad) and lp_conv16_wgrad.  in_scale: device scalar|NULL.
  * fp16 gradient operands: amax_part = amax_count partial maxima of |x|, amax_stride floats apart (|NULL) -- the lp_amax_blocks()

@@ -41,8 +41,10 @@ __global__ __launch_bounds__(256) void act_pack_kernel(const float* __restrict__
     const unsigned stride = gridDim.x * 256u;
     const int n = blockIdx.y;
     const bool vec = (C & 3) == 0;
-    const float lo_clamp = (pro != 0 && pro != 5) ? 0.f : -3.0e38f;
-    const float hi_clamp = (pro == 3) ? 6.f : 3.0e38f;          // pro 3 = ReLU6, 4 = ReLU, 5 = identity of a per-channel (batch-norm) affine
+    // pro 3 = ReLU6, 4 = ReLU, 5 = identity of a per-channel (batch-norm) affine; the identity bounds are infinite: an infinite activation stays infinite in
+    // the bf16 modes (the fp16 conversion saturates it), as the header states
+    const float lo_clamp = (pro != 0 && pro != 5) ? 0.f : -INFINITY;
+    const float hi_clamp = (pro == 3) ? 6.f : INFINITY;
     const bool aff = (pro == 1 || pro >= 3);
     const size_t aoff = (pro == 1) ? (size_t)n * C : 0;
     const float* xn = x + (size_t)n * HW * C;
@@ -87,7 +89,9 @@ __global__ __launch_bounds__(256) void act_pack_kernel(const float* __restrict__
                 s16x8_t h, l;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    float q = fminf(fmaxf(fmaf(v[u][j], sc[j], sf[j]), lo_clamp), hi_clamp) * isc;
+                    const float a = fmaf(v[u][j], sc[j], sf[j]);
+                    float q = fminf(fmaxf(a, lo_clamp), hi_clamp);
+                    q = ((a != a) ? a : q) * isc;                    // fmaxf / fminf return the other operand for a NaN: keep it (lp_f32_to_op16: a diverging run is not masked)
                     q = (c + j < C) ? q : 0.f;
                     const uint16_t hb = lp_f32_to_op16<F16>(q);
                     h[j] = (short)hb;

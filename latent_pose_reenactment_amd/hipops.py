@@ -84,7 +84,7 @@ def _pack_geometry(w: Tensor, mode: int, small_k: bool):
 
 def pack_weights(w: Tensor, mode: int, prec: int, small_k: bool = False) -> WeightPack:
     """w: [Cout, Cin, k, k] (or [Cout, Cin]) fp32.  mode 0 = forward pack, mode 1 = dgrad pack (flipped + transposed); 2 / 3 = the phase forms
-    (forward / data gradient) of a x2-upsampled 3x3 conv.  small_k pads the contraction dim to 32 instead of 64 (only valid for 3x3
+    (forward / data gradient) of a x2-upsampled 3x3 conv; 4 / 5 = the same pair for a 3x3 conv followed by AvgPool2d(2) (include/lp_hip.h).  small_k pads the contraction dim to 32 instead of 64 (only valid for 3x3
     non-upsampled convs)."""
     _chk(w, 'w')
     cout, cin, taps, taps_out, rows, cols, rows_p, cols_p = _pack_geometry(w, mode, small_k)
@@ -244,7 +244,7 @@ def _amax_attach(out: Tensor, want: bool):
 def act_pack(x: Tensor, *, pro: int = 0, scale: Optional[Tensor] = None, shift: Optional[Tensor] = None, prec: int = PREC_BF16,
              grad: bool = False) -> Act16:
     """x [N,H,W,C] fp32 -> operand planes of act(x): pro 0 identity | 1 relu(x*scale[n,c]+shift[n,c]) | 2 relu(x) |
-    3 relu6(x*scale[c]+shift[c]).
+    3 relu6(x*scale[c]+shift[c]) | 4 relu(x*scale[c]+shift[c]) | 5 x*scale[c]+shift[c] (3 .. 5: a BatchNorm folded to a per-channel affine).
     ``grad``: x is a gradient (dY): in fp16 mode it is scaled by a power of two taken from its amax (two extra small launches) so
     that it sits in the fp16 normal range; the consumer gets 1/scale through ``Act16.inv``."""
     _chk(x, 'x')
