@@ -542,6 +542,19 @@ int lp_augment_triplet(const float* pose, const long long* pose_strides, const f
 int lp_frames_prepare(const unsigned char* buf, long long buf_bytes, const long long* table_host, const long long* table_dev, int rows, int S,
                       float* image, int n_image, float* mask, int n_mask, float* product, int n_product, void* stream);
 
+/* (additive, ABI 12) Panel sheet of the training visuals (csrc/visual_sheet.hip holds the definition; the reference's utils/visualize.py:
+ * make_visual): P panels (1 .. 12) side by side, one row of panels per sample.  panels = HOST array of P DEVICE pointers, each a logical
+ * [N][C][H][W] fp32 tensor read in place; strides = HOST array [P][4] of element strides (image, channel, row, column; 0 allowed: an expanded view,
+ * negative refused); channels = HOST array [P], each 1 or 3 (1: the value goes to all three output channels); all three are read at call time and
+ * passed to the kernel by value.  caption (|NULL with Hc == 0): DEVICE uint8 [Hc][P W] greys, replicated to three channels on top of the sheet.
+ * out: DEVICE uint8 [Hc + N H][P W][3], contiguous HWC; sample n at rows Hc + n H ..., panel p at columns p W ....
+ * Value rule: (uint8) floor(min(max(x, 0), 1) * 255) with the multiplication in fp32; NaN gives 0.
+ * ONE launch, no atomics (bit-reproducible), no workspace, no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer (a panel's included), P outside 1 .. 12, N, H or W < 1, C outside {1, 3}, Hc < 0, Hc > 0 with a null caption, a negative
+ * stride -- checked before any device work. */
+int lp_visual_sheet(const float* const* panels, const long long* strides, const int* channels, int P, int N, int H, int W,
+                    const unsigned char* caption, int Hc, unsigned char* out, void* stream);
+
 /* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.

@@ -112,7 +112,8 @@ SIGNATURES = {
     'lp_image_quality': (_i, [_vp] * 6 + [_i] * 4 + [_vp, _vp, _vp]),
     'lp_augment_triplet': (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 4),
     'lp_frames_prepare': (_i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
-    'lp_pool_grad_pack': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    'lp_visual_sheet': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'lp_head_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -2,7 +2,8 @@
 """Reenactment ("driving") entry point with the reference's CLI (drive.py:19-98): load a fine-tuned checkpoint, take the
 EMA weights, and for every driving frame run ``embedder.get_pose_embedding`` + ``generator`` (HIP kernels, eval mode: the
 spectral norms are constant so the packed bf16 weights are reused).  The reference writes an .mp4 through cv2 (absent here,
-out of scope): frames are written as one .npy uint8 array [T, H, 2W, 3] (driver | result) per driving sequence instead."""
+out of scope): frames are written as one .npy uint8 array [T, H, 2W, 3] (driver | result) per driving sequence instead, or with
+``--format png`` as one PNG per frame, <destination>/<driver>/<frame:06>.png (PIL)."""
 import argparse
 import copy
 import logging
@@ -71,6 +72,18 @@ def drive_frame(embedder, generator, data_dict):
     return drive_frames(embedder, generator, data_dict)[0]
 
 
+def write_png_frames(directory, video):
+    """``video``: uint8 [T, H, W, 3] on the host -> <directory>/<frame:06>.png, one lossless file per frame; returns the paths"""
+    from PIL import Image
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    paths = []
+    for t, frame in enumerate(video):
+        paths.append(directory / f'{t:06}.png')
+        Image.fromarray(np.ascontiguousarray(frame)).save(paths[-1])
+    return paths
+
+
 def main():
     logging.basicConfig(level=logging.INFO, stream=sys.stdout, format="%(asctime)s - %(levelname)s - %(message)s")
     logger = logging.getLogger('drive')
@@ -81,6 +94,8 @@ def main():
     ap.add_argument('--images_paths', type=Path, nargs='+')
     ap.add_argument('--destination', type=Path, required=True)
     ap.add_argument('--batch_size', type=int, default=1, help='driving frames per generator call (the reference drives one frame at a time)')
+    ap.add_argument('--format', choices=('npy', 'png'), default='npy',
+                    help='npy: one uint8 array [T, H, 2W, 3] per driving sequence; png: the same frames as <destination>/<driver>/<frame:06>.png')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('drive.py needs the MI355X: the generator has no CPU fallback')
@@ -98,7 +113,11 @@ def main():
             utils.dict_to_device(data_dict, device)
             frames.append(drive_frames(embedder, generator, data_dict))       # uint8 on the device: nothing waits for the GPU here
         video = torch.cat(frames).cpu().numpy()                             # one device-to-host transfer (and sync) per sequence
-        np.save(out, video)
+        if args.format == 'png':
+            out = out.with_suffix('')
+            write_png_frames(out, video)
+        else:
+            np.save(out, video)
         logger.info(f'wrote {len(video)} frames to {out}')
 
 

@@ -1318,6 +1318,91 @@ def frames_prepare(buf: Tensor, table: Tensor, size: int):
     return tuple(outs)
 
 
+VISUAL_SHEET_MAX_PANELS = 12
+
+
+def _visual_sheet_check(panels, caption, out):
+    """the argument rules of ``visual_sheet`` / ``visual_sheet_host`` (no device call) -> (panels as a list, N, H, W, Hc)"""
+    if isinstance(panels, torch.Tensor) or not hasattr(panels, '__len__'):
+        raise ValueError(f'visual_sheet: panels must be a sequence of 4-D fp32 tensors, got {type(panels).__name__}')
+    panels = list(panels)
+    if not 1 <= len(panels) <= VISUAL_SHEET_MAX_PANELS:
+        raise ValueError(f'visual_sheet: 1 .. {VISUAL_SHEET_MAX_PANELS} panels are supported, got {len(panels)} (more than 12 panels do not fit one launch)'
+                         if panels else 'visual_sheet: 1 .. 12 panels are supported, got 0')
+    for i, t in enumerate(panels):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'visual_sheet: panel {i} must be a tensor, got {type(t).__name__}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'visual_sheet: panel {i} must be fp32, got {t.dtype}')
+        if t.dim() != 4:
+            raise ValueError(f'visual_sheet: panel {i} must be 4-D [N, C, H, W], got shape {tuple(t.shape)}')
+        if t.shape[1] not in (1, 3):
+            raise ValueError(f'visual_sheet: panel {i} must have 1 or 3 channels, got C = {t.shape[1]}')
+        if (t.shape[0], t.shape[2], t.shape[3]) != (panels[0].shape[0], panels[0].shape[2], panels[0].shape[3]):
+            raise ValueError(f'visual_sheet: shape mismatch between panel 0 {tuple(panels[0].shape)} and panel {i} {tuple(t.shape)}: N, H and W are shared')
+        if t.device != panels[0].device:
+            raise ValueError(f'visual_sheet: panel {i} is on {t.device}, panel 0 on {panels[0].device}: '
+                             + ('it is not on the GPU' if not t.is_cuda else 'all panels must be on one device'))
+    n, _, h, w = panels[0].shape
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f'visual_sheet: empty panels {tuple(panels[0].shape)}')
+    hc = 0
+    if caption is not None:
+        if not (isinstance(caption, torch.Tensor) and caption.dtype == torch.uint8 and caption.dim() == 2 and caption.shape[1] == len(panels) * w):
+            raise ValueError(f'visual_sheet: the caption strip must be uint8 [Hc, P * W] = [Hc, {len(panels) * w}], got '
+                             + (f'{tuple(caption.shape)} {caption.dtype}' if isinstance(caption, torch.Tensor) else type(caption).__name__))
+        if caption.device != panels[0].device:
+            raise ValueError(f'visual_sheet: the caption strip is on {caption.device}, the panels on {panels[0].device}')
+        hc = caption.shape[0]
+    if out is not None:
+        shape = (hc + n * h, len(panels) * w, 3)
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
+                and out.device == panels[0].device):
+            raise ValueError(f'visual_sheet: out must be a contiguous uint8 tensor of shape {shape} on {panels[0].device}')
+    return panels, n, h, w, hc
+
+
+def visual_sheet_host(panels, caption: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """``visual_sheet`` in torch ops on the panels' own device -- the definition of csrc/visual_sheet.hip step for step: NaN -> 0, clamp to [0, 1],
+    times 255 in fp32, truncated to uint8; a one-channel panel in all three channels; samples below each other, panels side by side, the strip on top"""
+    panels, n, h, w, hc = _visual_sheet_check(panels, caption, out)
+    cols = []
+    for t in panels:
+        q = t.detach().nan_to_num(nan=0.0).clamp(0, 1).mul(255).to(torch.uint8)          # (+-inf become the largest floats: the clamp's bounds)
+        cols.append(q.expand(n, 3, h, w).permute(0, 2, 3, 1).reshape(n * h, w, 3))
+    sheet = torch.cat(cols, dim=1)
+    if hc:
+        sheet = torch.cat((caption[:, :, None].expand(hc, caption.shape[1], 3), sheet), dim=0)
+    if out is not None:
+        return out.copy_(sheet)
+    return sheet.contiguous()
+
+
+def visual_sheet(panels, caption: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """uint8 sheet [Hc + N H, P W, 3] (HWC, on the panels' device) of ``panels``, a sequence of 1 .. 12 fp32 tensors or views [N, C, H, W] with C in
+    {1, 3} and N, H, W shared: sample n in rows Hc + n H ..., panel p in columns p W ..., every value (uint8) floor(clamp(x, 0, 1) * 255), NaN -> 0
+    (the header comment of csrc/visual_sheet.hip); ``caption``: uint8 [Hc, P W] greys put on top.  Panels on the GPU: ONE launch on the current stream
+    (lp_visual_sheet), every panel read in place through its strides -- a ``[:n, 0]`` view of a batch tensor or an ``expand``ed mask is never
+    materialised; CPU panels: ``visual_sheet_host``.  ``out``: a contiguous uint8 tensor of the result's shape to write into.  No gradient."""
+    panels, n, h, w, hc = _visual_sheet_check(panels, caption, out)
+    if not panels[0].is_cuda:
+        return visual_sheet_host(panels, caption, out)
+    import ctypes
+    count = len(panels)
+    panels = [t.detach() for t in panels]
+    ptrs = (ctypes.c_void_p * count)(*[t.data_ptr() for t in panels])
+    strides = (ctypes.c_longlong * (4 * count))(*[s for t in panels for s in t.stride()])
+    chans = (ctypes.c_int * count)(*[t.shape[1] for t in panels])
+    if caption is not None:
+        caption = caption.contiguous()
+    with torch.cuda.device(panels[0].device):
+        if out is None:
+            out = torch.empty((hc + n * h, count * w, 3), dtype=torch.uint8, device=panels[0].device)
+        check(_lib.lib().lp_visual_sheet(ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(chans), count, n, h, w, _p(caption), hc,
+                                         out.data_ptr(), _stream()), 'lp_visual_sheet')
+    return out
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)

@@ -3,9 +3,10 @@
   zero_grad(G) -> loss_G.backward(retain_graph) -> [all-reduce] -> step(G) -> zero_grad(D) -> loss_D.backward() ->
   [all-reduce] -> step(D) -> EMA(0.999 | 0.972 when fine-tuning).
 The reference's apex ``Reducer`` is replaced by ``parallel.GradReducer`` (RCCL all-reduce over xGMI of exactly the
-gradients each optimizer is about to consume).  TensorBoard / image-grid logging branches (holycow.py:266-400) are
-observability and out of scope; scalar losses go to ``Meter`` as in the reference, and so do the ``--metrics`` plugins' values
-(``Metric_<name>``, on the iterations whose losses are read back)."""
+gradients each optimizer is about to consume).  TensorBoard is out of scope: scalar losses go to ``Meter`` as in the reference, and so do the
+``--metrics`` plugins' values (``Metric_<name>``, on the iterations whose losses are read back); the image grid of holycow.py:324-342 is written as
+a PNG with ``--visuals`` (``log_visuals``; the "other video" group and the fixed validation images, :344-387, need dataset lookups and are not
+provided)."""
 import contextlib
 import copy
 import os
@@ -34,6 +35,9 @@ def get_args(parser):
     parser.add('--log_frequency_fixed_images', type=int, default=2500)
     parser.add('--detailed_metrics', action='store_bool', default=True)
     parser.add('--num_visuals_per_img', default=2, type=int)
+    parser.add('--visuals', action='store_bool', default=False,
+               help='every --log_frequency_images iterations write a captioned panel sheet of --num_visuals_per_img samples of the batch, from '
+                    'the running-average weights, to <experiment_dir>/visuals/train_<iteration>.png')
     parser.add('--fixed_val_ids', action='append', type=int, default=[50, 100, 200, 250, 300])
     parser.add('--batch_size_inference', default=5, type=int)
     return parser
@@ -420,6 +424,51 @@ def _graphed_step(training_module, data_dict, target_dict, optimizer_G, optimize
     return g.all_data, g.losses_G, g.losses_D
 
 
+CROSS_DRIVING_KEYS = ('pose_input_rgbs', 'dec_stickmen', 'dec_keypoints')      # what drives a sample: taken from its neighbour for the "other person" group
+
+
+def visual_forward(training_module, data_dict, target_dict, args):
+    """the forward whose outputs are shown (holycow.py:327-335): no gradient, running-average weights, no losses, the mode ``--set_eval_mode_in_test``
+    asks for, on this iteration's batch with the labels as the only target; the mode the module was in is put back.  It writes no parameter, no
+    buffer and no optimizer state, and in eval mode draws no random number: the training trajectory is what it is without it.
+    Meta-training with more than one sample: every sample is also driven by its neighbour in the batch (sample i by the pose input of sample
+    i - 1: ``roll(1, 0)``) -- one more ``get_pose_embedding`` + generator call on the same modules -> ``pose_input_rgbs_other_person``,
+    ``fake_rgbs_other_person`` (and ``dec_stickmen_other_person`` for a family driven by stickmen)."""
+    was_training = training_module.training
+    training_module.train(not args.set_eval_mode_in_test)
+    try:
+        with torch.no_grad(), training_module.set_use_running_averages(), training_module.set_compute_losses(False):
+            all_data, _, _ = training_module(data_dict, {'label': target_dict['label']} if 'label' in target_dict else {})
+            fake = all_data.get('fake_rgbs')
+            if not getattr(args, 'finetune', False) and fake is not None and fake.shape[0] > 1:
+                averaged = training_module.running_averages and training_module.use_running_averages
+                embedder = training_module.running_averages['embedder'] if averaged else training_module.embedder
+                generator = training_module.running_averages['generator'] if averaged else training_module.generator
+                other = copy.copy(all_data)
+                for key in CROSS_DRIVING_KEYS:
+                    if torch.is_tensor(other.get(key)):
+                        other[key] = other[key].roll(1, 0)
+                embedder.get_pose_embedding(other)
+                generator(other)
+                for key in ('pose_input_rgbs', 'dec_stickmen', 'fake_rgbs'):
+                    if torch.is_tensor(other.get(key)):
+                        all_data[key + '_other_person'] = other[key]
+    finally:
+        training_module.train(was_training)
+    return all_data
+
+
+def log_visuals(training_module, data_dict, target_dict, args):
+    """``--visuals``, on the logging rank every ``--log_frequency_images`` iterations: the visual forward, then its panels as one captioned sheet of
+    ``--num_visuals_per_img`` samples -> <experiment_dir>/visuals/train_<iteration:08>.png (the reference hands the sheet to TensorBoard)."""
+    from latent_pose_reenactment_amd.utils import visualize
+    all_data = visual_forward(training_module, data_dict, target_dict, args)
+    all_data.pop('dec_stickmen', None)
+    path = os.path.join(str(args.experiment_dir), 'visuals', f'train_{args.iteration:08}.png')
+    visualize.save_png(path, visualize.sheet(all_data, n_samples=args.num_visuals_per_img))
+    return path
+
+
 def run_epoch(dataloader, training_module, optimizer_G, optimizer_D, epoch, args, phase, writer=None, saver=None):
     meter = Meter()
     if phase == 'train':
@@ -460,8 +509,12 @@ def run_epoch(dataloader, training_module, optimizer_G, optimizer_D, epoch, args
                 for name in metrics.keys():
                     meter.add(f'Metric_{name}', metrics.get_average(name), metrics.get_num_measurements(name))
         if phase == 'train':
+            if getattr(args, 'visuals', False) and getattr(args, 'logging', True) and getattr(args, 'rank', 0) == 0 \
+                    and args.iteration % max(1, int(args.log_frequency_images)) == 0:
+                # ``--visuals``: eager launches behind the step (behind the replay with --hip_graph, as the metrics above), on this iteration's batch
+                log_visuals(training_module, data_dict, target_dict, args)
             # The reference advances args.iteration inside its TensorBoard branch, i.e. on the logging rank only (holycow.py:319,
-            # 389-390) -- the rank that also names the checkpoints model_{iteration:08}.pth.  Logging is out of scope here, so the
+            # 389-390) -- the rank that also names the checkpoints model_{iteration:08}.pth.  Scalars go to the Meter, not to TensorBoard, so the
             # counter advances on every rank and every training iteration: same checkpoint names as a logging reference run.
             args.iteration += 1
         meter.add('Batch_time', time.time() - end)

@@ -3,7 +3,8 @@
 plugin loading, fine-tuning bootstrap, epoch loop and SIGINT/SIGTERM checkpointing.  Differences, all on purpose:
   * data-parallel training uses ``parallel.GradReducer`` (RCCL over xGMI) instead of apex.Reducer; the launcher contract is
     unchanged (``python -m torch.distributed.launch/run --nproc_per_node=N train.py ...``; ``--local_rank`` or LOCAL_RANK);
-  * the horovod (>8 GPU) branch is not provided (broken upstream); TensorBoard/visual logging is out of scope.
+  * the horovod (>8 GPU) branch is not provided (broken upstream); TensorBoard is out of scope: ``--visuals`` writes the training
+    image grid as PNG files instead (runners/holycow.py: log_visuals).
 Run from this directory (or with it on PYTHONPATH) so that ``generators.<name>`` etc. resolve to these plugins."""
 import os
 import sys
