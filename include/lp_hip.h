@@ -528,6 +528,16 @@ int lp_augment_triplet(const float* pose, const long long* pose_strides, const f
                        const float* segm, const long long* segm_strides, const float* params, int B, int C, int Cs, int H, int W,
                        float* pose_out, float* target_out, float* segm_out, void* stream);
 
+/* (additive, ABI 12) Second stage of the pose-input augmentation, for the pose image only (csrc/augment_extra.hip holds the definition; the
+ * reference's ElasticTransformation, MedianBlur, AddToSaturation and JpegCompression, dataloaders/common/augmentation.py:53-76): pose logical
+ * [B][3][H][W] fp32 read in place, pose_strides = 4 element strides (image, channel, row, column; HOST array read at call time).  params [B][16]
+ * fp32, contiguous, DEVICE: elastic_alpha, elastic_seed, median, saturation, jpeg_quality, 11 reserved zeros (hipops.AUG_EXTRA_COLUMNS); the
+ * all-zero row copies an input in [0, 1] bit for bit.  out [B][3][H][W]: contiguous, must not overlap pose.  Hashed elastic displacement with bilinear
+ * taps and reflect-101 border, 3 x 3 median, value-preserving saturation, 8 x 8 DCT quantisation with the IJG-scaled Annex-K tables (4:4:4), clamp.
+ * ONE launch, no atomics (bit-reproducible, independent of B), no workspace, no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer, B < 1, C != 3, H < 1 or W < 1; LP_ERR_UNSUPPORTED: B or H x W beyond one launch grid -- checked before any device work. */
+int lp_augment_extra(const float* pose, const long long* pose_strides, const float* params, int B, int C, int H, int W, float* out, void* stream);
+
 /* (additive, ABI 12) From decoded frames to network-ready tensors (csrc/frames.hip holds the definition; the reference's SampleLoader.load_sample,
  * dataloaders/voxceleb2_segmentation_nolandmarks.py:89-175): buf = buf_bytes uint8 on the DEVICE, the decoded frames of a batch packed back to
  * back; the table = rows x 24 int64 (frames.COLUMNS), given twice: table_host is read and checked at call time, table_dev is the same table on the

@@ -111,6 +111,7 @@ SIGNATURES = {
     'lp_image_quality_workspace_bytes': (_ll, [_i, _i, _i]),
     'lp_image_quality': (_i, [_vp] * 6 + [_i] * 4 + [_vp, _vp, _vp]),
     'lp_augment_triplet': (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 4),
+    'lp_augment_extra': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'lp_frames_prepare': (_i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'lp_visual_sheet': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),

@@ -3,7 +3,13 @@
 row of 32 floats per sample, ``hipops.AUG_COLUMNS`` -- and the row travels with the batch as ``data_dict['aug_params']``; the PIXELS are resampled
 and filtered where they are consumed, at the top of ``TrainingModule.forward`` (``apply``): one lp_augment_triplet launch on the GPU, or
 ``augment_triplet_host`` -- the same definition in fp32 torch ops -- for CPU tensors.  The definition, and what it leaves out of the reference's
-pipeline, is the header comment of csrc/augment.hip; tests/augment_restatement.py restates it in fp64."""
+pipeline, is the header comment of csrc/augment.hip; tests/augment_restatement.py restates it in fp64.
+
+A SECOND, opt-in stage (``--use_extra_pixelwise_augs``) adds four more of the reference's pixelwise augmenters to the pose image: elastic jitter,
+3 x 3 median, saturation and JPEG block quantisation.  ``ParametricAugmenter.sample_extra`` draws one row of 16 floats
+(``hipops.AUG_EXTRA_COLUMNS``) from a generator stream of its own, the row travels as ``data_dict['aug_params_extra']``, and ``apply`` runs
+lp_augment_extra -- one more launch -- on the first stage's pose output (``augment_extra_host`` for CPU tensors).  Definition and deviations:
+the header comment of csrc/augment_extra.hip; tests/augment_extra_restatement.py restates it in fp64."""
 import logging
 import math
 
@@ -12,6 +18,8 @@ import torch
 logger = logging.getLogger('augmentation')
 
 NCOLS = 32
+NCOLS_EXTRA = 16
+EXTRA_SLOTS = ('elastic', 'median', 'saturation', 'jpeg')          # the second stage's steps; sample_extra picks a subset of 0 .. 2 of them
 SLOTS = ('filter', 'noise', 'add', 'multiply', 'contrast')          # the pixelwise steps; SomeOf((0, 5)) picks a subset (augmentation.py:46)
 
 
@@ -19,6 +27,7 @@ def get_args(parser):
     parser.add('--use_pixelwise_augs', action='store_bool', default=False)
     parser.add('--use_affine_scale', action='store_bool', default=False)
     parser.add('--use_affine_shift', action='store_bool', default=False)
+    parser.add('--use_extra_pixelwise_augs', action='store_bool', default=False)
     return parser
 
 
@@ -29,12 +38,23 @@ def neutral_row():
     return row
 
 
+def neutral_row_extra():
+    """the second stage's row that changes nothing: all zeros"""
+    return torch.zeros(NCOLS_EXTRA)
+
+
+def extra_stream_seed(seed, index, visit):
+    """the seed of the generator that ``sample_extra`` draws from: the loaders' (seed, index, visit) seeding of ``sample`` with another additive
+    constant, so the two rows of a sample come from two streams and ``aug_params`` does not depend on the second stage's flag"""
+    return (seed * 1000003 + index) * 8191 + visit + 700001 + (1 << 40)
+
+
 def _uniform(g, lo, hi):
     return lo + (hi - lo) * float(torch.rand((), generator=g))
 
 
 def _filter_taps(g):
-    """one of the reference's four 3 x 3 filters (augmentation.py:49-57; MedianBlur is not provided) -> 9 taps, row-major"""
+    """one of the reference's four 3 x 3 filters (augmentation.py:49-57; MedianBlur is a step of the second stage) -> 9 taps, row-major"""
     kind = int(torch.randint(0, 4, (), generator=g))
     ident = [0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0]
     if kind == 0:                                                   # GaussianBlur((0, 1.0)): sampled on 3 x 3 and normalised
@@ -65,17 +85,47 @@ class ParametricAugmenter:
         self.width = self.height = int(getattr(args, 'image_size', 256))
         if getattr(args, 'inference', False):
             logger.info("`args.inference` is set, so switching off all augmentations")
-            self.pixelwise = self.scale = self.shift = False
+            self.pixelwise = self.scale = self.shift = self.extra = False
             return
         self.pixelwise = bool(getattr(args, 'use_pixelwise_augs', False))
         self.scale = bool(getattr(args, 'use_affine_scale', False))
         self.shift = bool(getattr(args, 'use_affine_shift', False))
+        self.extra = bool(getattr(args, 'use_extra_pixelwise_augs', False))
         logger.info(f"Pixelwise augmentation: {self.pixelwise}")
         logger.info(f"Affine scale augmentation: {self.scale}")
         logger.info(f"Affine shift augmentation: {self.shift}")
+        logger.info(f"Extra pixelwise augmentation: {self.extra}")
 
     def is_empty(self):
-        return not (self.pixelwise or self.scale or self.shift)
+        return not (self.pixelwise or self.scale or self.shift or self.extra)
+
+    def has_first_stage(self):
+        """does any of the reference's three flags ask for an ``aug_params`` row"""
+        return self.pixelwise or self.scale or self.shift
+
+    def has_extra_stage(self):
+        """does ``--use_extra_pixelwise_augs`` ask for an ``aug_params_extra`` row"""
+        return self.extra
+
+    def sample_extra(self, generator):
+        """one row of the second stage (16 floats, ``hipops.AUG_EXTRA_COLUMNS``), drawn from ``generator`` -- a stream of its own
+        (``extra_stream_seed``) -- with the reference's ranges: a random subset of 0 .. 2 of the four steps (in place of ``SomeOf((0, 5))`` of
+        eleven, augmentation.py:46, of which these are four); the neutral row when the flag is off"""
+        g, row = generator, neutral_row_extra()
+        if not self.extra:
+            return row
+        count = int(torch.randint(0, 3, (), generator=g))
+        chosen = [EXTRA_SLOTS[i] for i in torch.randperm(len(EXTRA_SLOTS), generator=g)[:count].tolist()]
+        if 'elastic' in chosen and float(torch.rand((), generator=g)) < 0.5:          # sometimes(ElasticTransformation(alpha=(0.5, 3.5), sigma=0.15))
+            row[0] = _uniform(g, 0.5, 3.5)
+            row[1] = float(int(torch.randint(0, 1 << 24, (), generator=g)))
+        if 'median' in chosen:                                                       # MedianBlur(k=(1, 3)): k = 3 is the only effect
+            row[2] = 1.0
+        if 'saturation' in chosen:                                                   # AddToSaturation((-20, 20))
+            row[3] = _uniform(g, -20.0, 20.0) / 255.0
+        if 'jpeg' in chosen:                                                         # JpegCompression((70, 99)), taken as the quality
+            row[4] = float(int(torch.randint(70, 100, (), generator=g)))
+        return row
 
     def sample(self, generator):
         """one parameter row, drawn from ``generator`` (a CPU torch.Generator) with the reference's probabilities and ranges"""
@@ -238,12 +288,139 @@ def augment_triplet_host(pose, params, target=None, segm=None):
             None if s4 is None else (segm_out.unsqueeze(1) if s5 else segm_out))
 
 
+# ---- the second stage in fp32 torch ops (host) ---------------------------------------------------------------------------------------------------------
+EXTRA_KEY = 0x85EBCA6B
+S0 = 20.0 / 255.0
+QBASE = (          # ITU-T T.81 Annex K, tables K.1 (luminance) and K.2 (chrominance), row-major with the vertical frequency as the row
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32)
+
+
+def quant_tables(quality):
+    """(luminance, chrominance) 8 x 8 fp32 quantisation tables of an integer quality 1 .. 100: the base tables scaled by the IJG rule"""
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(torch.tensor([min(max((v * scale + 50) // 100, 1), 255) for v in base], dtype=torch.float32).reshape(8, 8) for base in QBASE)
+
+
+def _dct_matrix():
+    k, n = torch.arange(8, dtype=torch.float64)[:, None], torch.arange(8, dtype=torch.float64)[None, :]
+    c = 0.5 * torch.cos((2.0 * n + 1.0) * k * math.pi / 16.0)
+    c[0] = math.sqrt(1.0 / 8.0)
+    return c.to(torch.float32)
+
+
+def _elastic_host(img, alpha, seed):
+    c, h, w = img.shape
+    y = torch.arange(h, dtype=torch.int64)[:, None].expand(h, w)
+    x = torch.arange(w, dtype=torch.int64)[None, :].expand(h, w)
+    n = (y * w + x) & 0xFFFFFFFF
+    key = (int(seed) * EXTRA_KEY) & 0xFFFFFFFF
+    ux = (_mix32(((2 * n) & 0xFFFFFFFF) ^ key) >> 8).to(torch.float32) * 2.0 ** -23 - 1.0
+    uy = (_mix32(((2 * n + 1) & 0xFFFFFFFF) ^ key) >> 8).to(torch.float32) * 2.0 ** -23 - 1.0
+    a = torch.tensor(alpha, dtype=torch.float32)
+    xs, ys = x.to(torch.float32) + a * ux, y.to(torch.float32) + a * uy
+    x0f, y0f = torch.floor(xs), torch.floor(ys)
+    fx, fy = xs - x0f, ys - y0f
+    x0, y0 = x0f.clamp(-1.0e9, 1.0e9).to(torch.int64), y0f.clamp(-1.0e9, 1.0e9).to(torch.int64)
+
+    def tap(yy, xx):
+        return img[:, _reflect101(yy, h), _reflect101(xx, w)]
+    top = tap(y0, x0) * (1.0 - fx) + tap(y0, x0 + 1) * fx
+    bot = tap(y0 + 1, x0) * (1.0 - fx) + tap(y0 + 1, x0 + 1) * fx
+    return top * (1.0 - fy) + bot * fy
+
+
+def _median_host(img):
+    c, h, w = img.shape
+    yr = _reflect101(torch.arange(-1, h + 1, dtype=torch.int64), h)
+    xr = _reflect101(torch.arange(-1, w + 1, dtype=torch.int64), w)
+    wide = img[:, yr][:, :, xr]
+    nine = torch.stack([wide[:, i:i + h, j:j + w] for i in range(3) for j in range(3)])
+    return nine.sort(0).values[4]
+
+
+def _saturation_host(img, d):
+    big, small = img.max(0).values, img.min(0).values
+    s = torch.where(big > 0, (big - small) / torch.where(big > 0, big, torch.ones_like(big)), torch.zeros_like(big))
+    t = s.clamp(min=torch.tensor(S0, dtype=torch.float32).item())
+    g = (t + torch.tensor(d, dtype=torch.float32)).clamp(0.0, 1.0) / t
+    return big[None] - (big[None] - img) * g[None]
+
+
+def _jpeg_host(img, quality):
+    c, h, w = img.shape
+    hp, wp = -(-h // 8) * 8, -(-w // 8) * 8
+    yy, xx = torch.arange(hp).clamp(max=h - 1), torch.arange(wp).clamp(max=w - 1)
+    r, g, b = (255.0 * img[:, yy][:, :, xx]).unbind(0)
+    planes = torch.stack([0.299 * r + 0.587 * g + 0.114 * b - 128.0, -0.168736 * r - 0.331264 * g + 0.5 * b, 0.5 * r - 0.418688 * g - 0.081312 * b])
+    ql, qc = quant_tables(quality)
+    q = torch.stack([ql, qc, qc])[:, None, None]                                          # [3, 1, 1, 8, 8]
+    cm = _dct_matrix()
+    blocks = planes.reshape(3, hp // 8, 8, wp // 8, 8).permute(0, 1, 3, 2, 4)              # [3, by, bx, 8, 8]
+    coef = cm @ (blocks @ cm.t())                                                        # rows first, then columns
+    coef = q * torch.round(coef / q)                                                      # (torch.round: ties to even)
+    back = (cm.t() @ coef) @ cm                                                          # columns first, then rows
+    yv, cb, cr = back.permute(0, 1, 3, 2, 4).reshape(3, hp, wp)[:, :h, :w].unbind(0)
+    yv = yv + 128.0
+    return torch.stack([yv + 1.402 * cr, yv - 0.344136 * cb - 0.714136 * cr, yv + 1.772 * cb]) / 255.0
+
+
+def augment_extra_host(pose, params_extra):
+    """``hipops.augment_extra`` for CPU tensors: the definition of csrc/augment_extra.hip in fp32 torch ops, step for step (neutral steps skipped)"""
+    for name, t in (('pose', pose), ('params_extra', params_extra)):
+        if t.dtype != torch.float32:
+            raise ValueError(f'augment_extra_host: {name} must be fp32, got {t.dtype}')
+    if pose.dim() == 5 and pose.shape[1] == 1:
+        p4 = pose[:, 0]
+    elif pose.dim() == 4:
+        p4 = pose
+    else:
+        raise ValueError(f'augment_extra_host: pose must be [B, 3, H, W] or [B, 1, 3, H, W], got shape {tuple(pose.shape)}')
+    b, c, h, w = p4.shape
+    if c != 3:
+        raise ValueError(f'augment_extra_host: pose must have 3 channels, got C = {c}')
+    if tuple(params_extra.shape) != (b, NCOLS_EXTRA):
+        raise ValueError(f'augment_extra_host: params_extra must be [B, 16] = {(b, NCOLS_EXTRA)}, got {tuple(params_extra.shape)}')
+    p4 = p4.detach()
+    out = torch.empty(p4.shape, dtype=torch.float32)
+    for i in range(b):
+        alpha, seed, median, d, quality = params_extra[i].detach().tolist()[:5]
+        v = p4[i]
+        if alpha != 0.0:
+            v = _elastic_host(v, alpha, int(min(max(seed, 0.0), 16777215.0)))
+        if median != 0.0:
+            v = _median_host(v)
+        if d != 0.0:
+            v = _saturation_host(v, d)
+        if quality != 0.0:
+            v = _jpeg_host(v, int(min(max(quality, 1.0), 100.0)))
+        out[i] = v.clamp(0.0, 1.0)
+    return out.reshape(pose.shape)
+
+
+def _apply_extra(pose, extra):
+    if pose.is_cuda:
+        from latent_pose_reenactment_amd import hipops
+        return hipops.augment_extra(pose, extra)
+    return augment_extra_host(pose, extra)
+
+
 def apply(data_dict, target_dict):
     """-> shallow copies of the two dicts in which ``pose_input_rgbs``, ``target_rgbs`` and ``real_segm`` (whichever are there, in either dict) are
-    replaced by their augmented versions, and from which ``aug_params`` ([B, 32]) is gone: it is consumed here.  CUDA tensors go through ONE
-    lp_augment_triplet launch on the current stream (graph-safe: no host read of the parameters), CPU tensors through ``augment_triplet_host``."""
+    replaced by their augmented versions, and from which ``aug_params`` ([B, 32]) and ``aug_params_extra`` ([B, 16]) are gone: they are consumed
+    here.  ``aug_params``: CUDA tensors go through ONE lp_augment_triplet launch on the current stream (graph-safe: no host read of the parameters),
+    CPU tensors through ``augment_triplet_host``.  ``aug_params_extra``: the pose image -- the first stage's output when both keys are there --
+    goes through ONE lp_augment_extra launch, or ``augment_extra_host``.  With the second key alone the first stage is not launched."""
     data_dict = dict(data_dict)
     target_dict = dict(target_dict) if isinstance(target_dict, dict) else target_dict
+    extra = data_dict.pop('aug_params_extra', None)
+    if extra is not None and 'aug_params' not in data_dict:
+        where =data_dict if torch.is_tensor(data_dict.get('pose_input_rgbs')) else (target_dict if isinstance(target_dict, dict) else {})
+        if not torch.is_tensor(where.get('pose_input_rgbs')):
+            raise KeyError("augmentation.apply: the batch carries 'aug_params_extra' but no 'pose_input_rgbs'")
+        where['pose_input_rgbs'] = _apply_extra(where['pose_input_rgbs'], extra)
+        return data_dict, target_dict
     params = data_dict.pop('aug_params')
     dicts = [data_dict] + ([target_dict] if isinstance(target_dict, dict) else [])
 
@@ -263,6 +440,8 @@ def apply(data_dict, target_dict):
         outs = hipops.augment_triplet(pose, params, target, segm)
     else:
         outs = augment_triplet_host(pose, params, target, segm)
+    if extra is not None:
+        outs = (_apply_extra(outs[0], extra),) + tuple(outs[1:])
     for key, out in zip(('pose_input_rgbs', 'target_rgbs', 'real_segm'), outs):
         if out is not None:
             where[key][key] = out

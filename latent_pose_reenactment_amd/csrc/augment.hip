@@ -37,6 +37,7 @@
 //   * a fixed order of the steps where the reference shuffles them (random_order=True, :79 and :103);
 //   * one 3 x 3 filter slot per sample where SomeOf can chain blur, sharpen and emboss (:46-57);
 //   * not provided: MedianBlur (:53), JpegCompression (:68), ElasticTransformation (:76), the simplex-noise edge blend (:60-62), AddToSaturation (:67).
+//     (Not provided HERE: all but the edge blend are the opt-in second stage, one more launch on the pose image -- csrc/augment_extra.hip.)
 //
 // One workgroup = one role (pose | target | segm) x one image x one 16 x 16 output tile; role and image are blockIdx.z.  A lane owns one channel of
 // four consecutive pixels of a row (C x 16 rows x 4 quads <= 256 lanes) and stores them with one 16-byte store when W % 4 == 0 (and the outputs are

@@ -4,7 +4,10 @@
   data_dict:   ... + aug_params 32 floats (hipops.AUG_COLUMNS): what the augmenter drew for this sample
 and the pixels are augmented on the device at the top of the training forward (augmentation.apply).  The draw is seeded from (seed, index, how often
 this index has been served) for ``part == 'train'`` -- every visit of a sample sees another augmentation -- and from (seed, index) alone otherwise:
-the reference's ``deterministic_`` for validation.  With all three flags off (or ``--inference``) no ``aug_params`` is emitted."""
+the reference's ``deterministic_`` for validation.  With all three flags off (or ``--inference``) no ``aug_params`` is emitted.
+``--use_extra_pixelwise_augs`` adds, independently of the three,
+  data_dict:   ... + aug_params_extra 16 floats (hipops.AUG_EXTRA_COLUMNS): the second stage's row (elastic, median, saturation, JPEG)
+drawn from a generator stream of its own with the same (seed, index, visit) seeding."""
 import torch
 
 from latent_pose_reenactment_amd import augmentation
@@ -35,5 +38,9 @@ class Dataset(_base.Dataset):
                 visit = self.visits.get(index, 0)
                 self.visits[index] = visit + 1
             g = torch.Generator().manual_seed((self.seed * 1000003 + index) * 8191 + visit + 700001)     # (its own stream, as the keypoints have)
-            data['aug_params'] = self.augmenter.sample(g)
+            if self.augmenter.has_first_stage():
+                data['aug_params'] = self.augmenter.sample(g)
+            if self.augmenter.has_extra_stage():          # the second stage's row: a stream of its own, so aug_params does not depend on the flag
+                data['aug_params_extra'] = self.augmenter.sample_extra(
+                    torch.Generator().manual_seed(augmentation.extra_stream_seed(self.seed, index, visit)))
         return data, target

@@ -6,7 +6,7 @@ PIL and returns them as raw uint8 bytes with the rows of the table that describe
 bytes and rebases the offsets; the loader returned by ``get_dataloader`` copies the packed bytes to the device once and makes the batch there
 (``frames.prepare``: crop to the scaled bounding box, resize, / 255, image x segmentation in one lp_frames_prepare launch).  What it yields is
 ``synthetic_voxceleb2``'s contract:
-  data_dict:   enc_rgbs B x K x 3 x S x S, pose_input_rgbs B x 1 x 3 x S x S, target_rgbs B x 1 x 3 x S x S (+ aug_params B x 32 when augmenting)
+  data_dict:   enc_rgbs B x K x 3 x S x S, pose_input_rgbs B x 1 x 3 x S x S, target_rgbs B x 1 x 3 x S x S (+ aug_params B x 32 / aug_params_extra B x 16 when augmenting)
   target_dict: real_segm B x 1 x 3 x S x S, label int64 B
 and under ``--inference`` only what the reference loads then (fine-tuning form: enc_rgbs = pose_input_rgbs and the label; otherwise the encoder
 frames and the label).  Keypoints and stickmen (the FSTH family) are not read.  Not provided: the blur and fade of padded bands (csrc/frames.hip)."""
@@ -252,20 +252,31 @@ class FrameLoader:
         return len(self.loader)
 
     def _aug_params(self, indices):
-        rows = []
+        """-> {'aug_params': [B, 32]} and / or {'aug_params_extra': [B, 16]}, whichever the flags ask for; the two rows of a sample come from two
+        generator streams, so ``aug_params`` is the same with and without the second stage"""
+        rows, extra = [], []
         for index in indices:
             visit = 0
             if self.part == 'train':
                 visit = self.visits.get(index, 0)
                 self.visits[index] = visit + 1
-            g = torch.Generator().manual_seed((self.seed * 1000003 + index) * 8191 + visit + 700001)
-            rows.append(self.augmenter.sample(g))
-        return torch.stack(rows)
+            if self.augmenter.has_first_stage():
+                g = torch.Generator().manual_seed((self.seed * 1000003 + index) * 8191 + visit + 700001)
+                rows.append(self.augmenter.sample(g))
+            if self.augmenter.has_extra_stage():
+                g = torch.Generator().manual_seed(augmentation.extra_stream_seed(self.seed, index, visit))
+                extra.append(self.augmenter.sample_extra(g))
+        out = {}
+        if rows:
+            out['aug_params'] = torch.stack(rows)
+        if extra:
+            out['aug_params_extra'] = torch.stack(extra)
+        return out
 
     def __iter__(self):
         for raw in self.loader:
             if not self.augmenter.is_empty():
-                raw = dict(raw, aug_params=self._aug_params(raw['index'].tolist()))
+                raw = dict(raw, **self._aug_params(raw['index'].tolist()))
             yield frames.prepare(raw, self.size, self.device)
 
 

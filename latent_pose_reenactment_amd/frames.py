@@ -11,7 +11,7 @@ the three outputs (image, mask, product) is written to (-1: not written).  A raw
   table   int64 [R, 24]      offsets relative to ``buf``
   frames  K                  encoder frames per sample (slots b K + k of ``image``); 0: ``enc_rgbs`` and ``pose_input_rgbs`` are one image
   pose    bool               rows with the pose image follow at the slots B K + b
-  label   int64 [B]          (+ aug_params [B, 32] when the loader augments)"""
+  label   int64 [B]          (+ aug_params [B, 32] / aug_params_extra [B, 16] when the loader augments)"""
 import logging
 import math
 
@@ -254,5 +254,7 @@ def prepare(raw_batch, size, device):
         target_dict['real_segm'] = mask.view(b, 1, 3, size, size)
     if 'aug_params' in raw_batch:
         data_dict['aug_params'] = raw_batch['aug_params'].to(device, non_blocking=True)
+    if 'aug_params_extra' in raw_batch:
+        data_dict['aug_params_extra'] = raw_batch['aug_params_extra'].to(device, non_blocking=True)
     target_dict['label'] = label.to(device, non_blocking=True)
     return data_dict, target_dict

@@ -1296,6 +1296,61 @@ def augment_triplet(pose: Tensor, params: Tensor, target: Optional[Tensor] = Non
             None if s4 is None else (outs[2].unsqueeze(1) if s5 else outs[2]))
 
 
+AUG_EXTRA_COLUMNS = ('elastic_alpha', 'elastic_seed', 'median', 'saturation', 'jpeg_quality') + tuple(f'reserved{i}' for i in range(11))
+
+
+def augment_extra(pose: Tensor, params_extra: Tensor, out: Optional[Tensor] = None):
+    """pose' of the second augmentation stage defined in the header comment of csrc/augment_extra.hip: ``params_extra`` [B, 16]
+    (``AUG_EXTRA_COLUMNS``) holds per sample the elastic amplitude and seed, the median switch, the saturation offset and the JPEG quality; the
+    all-zero row returns an input in [0, 1] bit for bit.  ``pose``: [B, 3, H, W] or [B, 1, 3, H, W], read in place through its strides (a ``[:, 0]``
+    view is never materialised); the result has its shape.  ``out``: a contiguous fp32 tensor of that shape on the same device, not sharing storage
+    with ``pose`` (a slice of a larger buffer is fine), written and returned; None allocates.  ONE launch on the current stream
+    (lp_augment_extra), bit-reproducible.  No gradient."""
+    for name, t in (('pose', pose), ('params_extra', params_extra)) + ((('out', out),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'augment_extra: {name} must be a tensor, got {type(t).__name__}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'augment_extra: {name} must be fp32, got {t.dtype}')
+    if pose.dim() == 5 and pose.shape[1] == 1:
+        p4 = pose[:, 0]
+    elif pose.dim() == 4:
+        p4 = pose
+    else:
+        raise ValueError(f'augment_extra: pose must be [B, 3, H, W] or [B, 1, 3, H, W], got shape {tuple(pose.shape)}')
+    b, c, h, w = p4.shape
+    if c != 3:
+        raise ValueError(f'augment_extra: pose must have 3 channels (saturation and JPEG are defined on RGB), got C = {c}')
+    if tuple(params_extra.shape) != (b, len(AUG_EXTRA_COLUMNS)):
+        raise ValueError(f'augment_extra: params_extra must be [B, 16] = {(b, len(AUG_EXTRA_COLUMNS))}, got {tuple(params_extra.shape)}')
+    if b < 1 or h < 1 or w < 1:
+        raise ValueError(f'augment_extra: empty input {tuple(pose.shape)}')
+    if b > 65535 or (h + 15) // 16 > 65535:
+        raise ValueError(f'augment_extra: B = {b} or H = {h} exceeds one launch grid (at most 65535 images and 65535 tiles of 16 rows)')
+    if out is not None:
+        if tuple(out.shape) != tuple(pose.shape):
+            raise ValueError(f'augment_extra: shape mismatch between pose {tuple(pose.shape)} and out {tuple(out.shape)}')
+        if not out.is_contiguous():
+            raise ValueError('augment_extra: out must be contiguous')
+    for name, t in (('pose', pose), ('params_extra', params_extra)) + ((('out', out),) if out is not None else ()):
+        if not t.is_cuda:
+            raise ValueError(f'augment_extra: {name} is on {t.device}: all tensors must be CUDA tensors (the host version is '
+                             'augmentation.augment_extra_host)')
+        if t.device != pose.device:
+            raise ValueError(f'augment_extra: mixed devices: {name} is on {t.device}, pose on {pose.device}')
+    if out is not None and out.untyped_storage().data_ptr() == pose.untyped_storage().data_ptr():
+        raise ValueError('augment_extra: out shares its storage with pose (elastic and median read neighbouring tiles: not an in-place operation)')
+    import ctypes
+    p4 = p4.detach()
+    par = params_extra.detach().contiguous()
+    strides = (ctypes.c_longlong * 4)(*p4.stride())
+    res = torch.empty(pose.shape, dtype=torch.float32, device=pose.device) if out is None else out
+    npix = b * h * w
+    with _Timed('augment_extra', 2.0 * npix * 3 * (12 + 32), (b, h, w, c, 16), (4 * npix * 3 + 64 * b, 4 * npix * 3)):
+        check(_lib.lib().lp_augment_extra(p4.data_ptr(), ctypes.addressof(strides), par.data_ptr(), b, c, h, w, res.data_ptr(), _stream()),
+              'lp_augment_extra')
+    return res
+
+
 def frames_prepare(buf: Tensor, table: Tensor, size: int):
     """(image, mask, product) of the frame preparation defined in the header comment of csrc/frames.hip: ``buf`` = the decoded uint8 frames of a
     batch, packed, on the device; ``table`` = int64 [R, 24] (``frames.COLUMNS``) on the HOST, one row per output image: an image view with its box

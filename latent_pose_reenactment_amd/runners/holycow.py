@@ -136,9 +136,10 @@ class TrainingModule(nn.Module):
         else:
             embedder, generator = self.embedder, self.generator
         data_dict = copy.copy(data_dict)          # inputs only; modules add their outputs
-        if 'aug_params' in data_dict:
+        if 'aug_params' in data_dict or 'aug_params_extra' in data_dict:
             # the loader drew an augmentation for every sample (dataloaders/synthetic_voxceleb2_augmented.py): pose image, target and mask are
             # replaced HERE, in one launch, before anything forks a side stream -- every module, criterion and metric sees the augmented tensors
+            # (aug_params_extra: one more launch on the pose image, behind the first)
             from latent_pose_reenactment_amd import augmentation
             data_dict, target_dict = augmentation.apply(data_dict, target_dict)
         # the target-image halves of the VGG criterions depend on neither encoder nor generator -- they start now, each on a side stream
