@@ -552,6 +552,21 @@ int lp_augment_extra(const float* pose, const long long* pose_strides, const flo
 int lp_frames_prepare(const unsigned char* buf, long long buf_bytes, const long long* table_host, const long long* table_dev, int rows, int S,
                       float* image, int n_image, float* mask, int n_mask, float* product, int n_product, void* stream);
 
+/* (additive, ABI 12) The padded bands of out-of-frame crops (csrc/frames_pad.hip holds the definition; the reference's crop_with_padding,
+ * dataloaders/voxceleb2_segmentation_nolandmarks.py:283-367): buf = buf_bytes uint8 on the DEVICE whose first head_bytes hold the packed frames and
+ * whose tail is the workspace.  The plan = plans x 16 int64 (frames.PLAN_COLUMNS: table row, view (0 image, 1 mask), the view's offset, H, W, row
+ * stride, pixel stride, the box's t, l and side n, the pads top, left, bottom, right, the blur's k, the workspace offset), given twice: plan_host is
+ * read and checked at call time, plan_dev is the same plan on the DEVICE.  weights: DEVICE fp32 [plans][100], the k Gaussian taps of each plan
+ * first.  hist: DEVICE uint32 [plans][3][256] and median: DEVICE fp32 [plans][3], scratch, contents irrelevant on entry.  Each plan row's n x n
+ * crop through the border rule, blurred, blended, faded to the median (mask: to 0) and rounded, is written as a dense uint8 [n][n][C] image at its
+ * workspace offset; nothing else of buf is written.  A clear and three launches (histogram with integer atomics, median, main); bit-reproducible
+ * and independent of the other plan rows; no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG (naming the plan and its table row): null pointer, plans outside 1 .. 65535, head_bytes outside 0 .. buf_bytes, a view outside the
+ * head, pads or k that the box does not give, a workspace image that is not 16-byte aligned, overlaps the head or the image before it, or leaves
+ * buf; LP_ERR_UNSUPPORTED: a crop above 1024 -- all checked before any device work. */
+int lp_frames_pad(unsigned char* buf, long long buf_bytes, long long head_bytes, const long long* plan_host, const long long* plan_dev, int plans,
+                  const float* weights, unsigned int* hist, float* median, void* stream);
+
 /* (additive, ABI 12) Panel sheet of the training visuals (csrc/visual_sheet.hip holds the definition; the reference's utils/visualize.py:
  * make_visual): P panels (1 .. 12) side by side, one row of panels per sample.  panels = HOST array of P DEVICE pointers, each a logical
  * [N][C][H][W] fp32 tensor read in place; strides = HOST array [P][4] of element strides (image, channel, row, column; 0 allowed: an expanded view,

@@ -113,6 +113,7 @@ SIGNATURES = {
     'lp_augment_triplet': (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 4),
     'lp_augment_extra': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'lp_frames_prepare': (_i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    'lp_frames_pad': (_i, [_vp, _ll, _ll, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'lp_visual_sheet': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

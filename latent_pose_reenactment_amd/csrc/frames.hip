@@ -33,8 +33,9 @@
 // contiguous real_segm); product[slot] = image x mask, one fp32 multiplication of the two values of this same workgroup (target_rgbs).
 //
 // Deviation from the reference, on purpose: crop_with_padding also blurs the padded bands, and a thin band inside them, with a Gaussian of
-// sigma = 0.016 n and fades them to the image's per-channel median (to 0 for masks) (:314-359).  This is NOT provided: padded bands carry the border
-// rule's pixels as they are.  For an already-cropped dataset (no bounding-box file) the reference's own arithmetic pads 1 pixel at the top and left
+// sigma = 0.016 n and fades them to the image's per-channel median (to 0 for masks) (:314-359).  This launch does not: padded bands carry the border
+// rule's pixels as they are.  The blur and fade are opt-in and live in csrc/frames_pad.hip, which writes such crops as dense uint8 images that this
+// launch then reads as plain in-view boxes of a rewritten table (frames.pad_plan).  Without it: for an already-cropped dataset (no bounding-box file) the reference's own arithmetic pads 1 pixel at the top and left
 // and 2 at the bottom and right of every frame, so the deviation touches a one- to two-pixel rim; for boxes that leave a raw frame it touches the
 // whole padded band.  uint8 rounding between the reference's steps (after the crop, after the resize) is not reproduced either.
 //

@@ -9,7 +9,9 @@ bytes and rebases the offsets; the loader returned by ``get_dataloader`` copies 
   data_dict:   enc_rgbs B x K x 3 x S x S, pose_input_rgbs B x 1 x 3 x S x S, target_rgbs B x 1 x 3 x S x S (+ aug_params B x 32 / aug_params_extra B x 16 when augmenting)
   target_dict: real_segm B x 1 x 3 x S x S, label int64 B
 and under ``--inference`` only what the reference loads then (fine-tuning form: enc_rgbs = pose_input_rgbs and the label; otherwise the encoder
-frames and the label).  Keypoints and stickmen (the FSTH family) are not read.  Not provided: the blur and fade of padded bands (csrc/frames.hip)."""
+frames and the label).  Keypoints and stickmen (the FSTH family) are not read.  ``--blur_padded_bands`` (off by default) blurs the padded bands
+of a box that leaves its frame and fades them to the median colour, as the reference's ``crop_with_padding`` does (csrc/frames_pad.hip); without
+it they carry the border rule's pixels as they are (csrc/frames.hip)."""
 import logging
 import random
 from itertools import chain
@@ -141,6 +143,8 @@ class Dataset(torch.utils.data.Dataset):
         parser.add('--draw_oval', default=True, action="store_bool")
         parser.add('--n_frames_for_encoder', default=8, type=int)
         parser.add('--num_labels', type=int, default=98000, help='identities in the training split; set from the split when training from scratch')
+        parser.add('--blur_padded_bands', default=False, action="store_bool",
+                   help='blur the padded bands of a box that leaves its frame and fade them to the median colour (crop_with_padding)')
         return augmentation.get_args(parser)
 
     @staticmethod
@@ -234,13 +238,14 @@ class Collate:
 
 class FrameLoader:
     """iterable of (data_dict, target_dict) over a torch DataLoader of raw batches: per batch one pinned host-to-device copy of the packed bytes and
-    one launch on the current stream (``frames.prepare``).  The augmentation parameters are drawn HERE, in the iterating process, so that they do not
+    one launch on the current stream (``frames.prepare``; with ``--blur_padded_bands`` the pad launches before it).  The augmentation parameters are drawn HERE, in the iterating process, so that they do not
     depend on the number of workers: seeded as ``synthetic_voxceleb2_augmented`` seeds them, from (seed, index, visit) for ``part == 'train'`` and from
     (seed, index) alone otherwise."""
 
     def __init__(self, loader, args, part):
         self.loader, self.dataset = loader, loader.dataset
         self.size, self.part = args.image_size, part
+        self.blur_padded_bands = bool(getattr(args, 'blur_padded_bands', False))
         device = str(getattr(args, 'device', 'cuda'))
         self.device = device if device.startswith('cuda') and torch.cuda.is_available() else 'cpu'
         self.augmenter = augmentation.ParametricAugmenter(args)
@@ -277,7 +282,7 @@ class FrameLoader:
         for raw in self.loader:
             if not self.augmenter.is_empty():
                 raw = dict(raw, **self._aug_params(raw['index'].tolist()))
-            yield frames.prepare(raw, self.size, self.device)
+            yield frames.prepare(raw, self.size, self.device, self.blur_padded_bands)
 
 
 def get_dataloader(args, part):

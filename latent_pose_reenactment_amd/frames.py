@@ -1,9 +1,14 @@
 """From decoded frames to the batch (reference: SampleLoader.load_sample, dataloaders/voxceleb2_segmentation_nolandmarks.py:89-175, and its
 ``crop_with_padding``, :283-367): the LOADER decodes uint8 frames and packs them back to back; the PIXELS -- crop to the bounding box through the
 border rule, resize to the network's resolution, / 255, image x segmentation -- are made where the batch is consumed: one lp_frames_prepare launch
-on the GPU (``hipops.frames_prepare``), or ``prepare_host`` -- the same definition in fp32 torch ops -- for CPU tensors.  The definition, and what
-it leaves out of the reference (the blur and fade of the padded bands), is the header comment of csrc/frames.hip; tests/frames_restatement.py
-restates it in fp64.
+on the GPU (``hipops.frames_prepare``), or ``prepare_host`` -- the same definition in fp32 torch ops -- for CPU tensors.  The definition is the
+header comment of csrc/frames.hip; tests/frames_restatement.py restates it in fp64.
+
+What the reference does beyond that where a box leaves its frame -- the blur of the padded bands and their fade to the median colour
+(``crop_with_padding``, :314-359) -- is opt-in (``blur_padded_bands``; the loader's ``--blur_padded_bands``) and defined by the header comment of
+csrc/frames_pad.hip (fp64: tests/frames_pad_restatement.py).  ``pad_plan`` finds the affected views and gives each a dense uint8 n x n image in a
+workspace behind the packed frames; ``hipops.frames_pad`` (lp_frames_pad) or ``pad_host`` fills those images; the preparation then runs unchanged
+on the rewritten table, in which they are plain in-view boxes.  Without the flag padded bands carry the border rule's pixels as they are.
 
 A table row (``COLUMNS``, int64) describes one output image: an image view with its box and mode, a mask view with its box, and the slot each of
 the three outputs (image, mask, product) is written to (-1: not written).  A raw batch, as the loader's collate function makes it:
@@ -12,6 +17,7 @@ the three outputs (image, mask, product) is written to (-1: not written).  A raw
   frames  K                  encoder frames per sample (slots b K + k of ``image``); 0: ``enc_rgbs`` and ``pose_input_rgbs`` are one image
   pose    bool               rows with the pose image follow at the slots B K + b
   label   int64 [B]          (+ aug_params [B, 32] / aug_params_extra [B, 16] when the loader augments)"""
+import functools
 import logging
 import math
 
@@ -29,6 +35,11 @@ MAX_SIZE = 4096
 MAX_COORD = 1 << 30
 CUBIC_A = -0.75
 _IMG, _MSK, _SLOTS = 0, 10, 19
+PLAN_COLUMNS = ('row', 'view', 'off', 'h', 'w', 'row_stride', 'pixel_stride', 't', 'l', 'n', 'pad_t', 'pad_l', 'pad_b', 'pad_r', 'k', 'ws_off')
+NPLAN = len(PLAN_COLUMNS)
+PAD_MAX_N = 1024                # k <= 99: the halo of a 16 x 16 tile, three channels, still fits LDS
+PAD_WEIGHT_ROW = 100
+PAD_ALIGN = 16
 
 
 def bbox_to_integer_coords(t, l, b, r, image_h, image_w):
@@ -185,10 +196,139 @@ def _resample(crop, size, mode):
     return out / 255.0
 
 
-def prepare_host(buf, table, size):
-    """``hipops.frames_prepare`` for CPU tensors: (image, mask, product), fp32 [slots, 3, size, size] each, None where no row asks"""
+# ---- the padded bands (csrc/frames_pad.hip) ----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=64)
+def blur_taps(n):
+    """-> the k Gaussian taps g[-R .. R] of a crop of side n, in fp64: k = cvRound(6 sigma + 1) | 1 with sigma = 0.016 n, in integers (no ties)"""
+    k = ((96 * n + 1500) // 1000) | 1
+    radius, sigma = (k - 1) // 2, 0.016 * n
+    g = [math.exp(-(a * a) / (2.0 * sigma * sigma)) for a in range(-radius, radius + 1)]
+    total = sum(g)
+    return tuple(v / total for v in g)
+
+
+def pad_plan(table, nbytes, size):
+    """the views of ``table`` whose box leaves them -> (rewritten table, plan int64 [P, 16] (``PLAN_COLUMNS``), weights fp32 [P, 100], total bytes).
+    Each such view gets a dense uint8 [n, n, C] image at ``ws_off`` (16-byte aligned) behind the ``nbytes`` packed bytes, and in the rewritten table it
+    is that image with the box 0, 0, n, n and the same mode; a row whose boxes lie inside their views is not touched and takes no workspace.  Pure
+    integer arithmetic on the host (the reserved columns are not read); ValueError naming the row for a padded crop above ``PAD_MAX_N``."""
+    check_table(table, nbytes, size)
+    rows = table.tolist()
+    plan, weights, end = [], [], nbytes
+    for i, r in enumerate(rows):
+        for view, (what, base, chans) in enumerate((('image', _IMG, 3), ('mask', _MSK, 1))):
+            if not r[base + 1]:
+                continue
+            off, h, w, rs, ps, t, l, b, rr = r[base:base + 9]
+            n = b - t
+            pads = [max(0, -t), max(0, -l), max(0, b - h), max(0, rr - w)]
+            if not any(pads):
+                continue
+            if n > PAD_MAX_N:
+                raise ValueError(f'frames: row {i}: the padded {what} crop of {n} is above {PAD_MAX_N} (the blur of the padded bands supports k <= 99)')
+            g = blur_taps(n)
+            ws = (end + PAD_ALIGN - 1) // PAD_ALIGN * PAD_ALIGN
+            end = ws + n * n * chans
+            plan.append([i, view, off, h, w, rs, ps, t, l, n] + pads + [len(g), ws])
+            weights.append(list(g) + [0.0] * (PAD_WEIGHT_ROW - len(g)))
+            r[base:base + 9] = [ws, n, n, n * chans, chans, 0, 0, n, n]
+    return (torch.tensor(rows, dtype=torch.int64), torch.tensor(plan, dtype=torch.int64).reshape(-1, NPLAN),
+            torch.tensor(weights, dtype=torch.float64).to(torch.float32).reshape(-1, PAD_WEIGHT_ROW), end)
+
+
+def check_plan(plan, weights, head_bytes, buf_bytes):
+    """ValueError naming the plan row for anything lp_frames_pad would refuse (the same rules, before any device work)"""
+    if not (torch.is_tensor(plan) and plan.dtype == torch.int64 and plan.dim() == 2 and plan.shape[1] == NPLAN and plan.shape[0] >= 1 and not plan.is_cuda):
+        raise ValueError(f'frames: the plan must be an int64 HOST tensor [plans >= 1, {NPLAN}]')
+    if not (torch.is_tensor(weights) and weights.dtype == torch.float32 and tuple(weights.shape) == (plan.shape[0], PAD_WEIGHT_ROW) and not weights.is_cuda):
+        raise ValueError(f'frames: the weights must be an fp32 HOST tensor [{plan.shape[0]}, {PAD_WEIGHT_ROW}]')
+    if not 0 <= head_bytes <= buf_bytes:
+        raise ValueError(f'frames: the packed head of {head_bytes} bytes must lie inside the buffer of {buf_bytes} bytes')
+    end = head_bytes
+    for i, (row, view, off, h, w, rs, ps, t, l, n, pt, pl, pb, pr, k, ws) in enumerate(plan.tolist()):
+        if view not in (0, 1):
+            raise ValueError(f'frames: plan {i} (row {row}): view {view} is neither 0 (image) nor 1 (mask)')
+        chans = 1 if view else 3
+        if n < 1:
+            raise ValueError(f'frames: plan {i} (row {row}): the crop has side {n} < 1')
+        if n > PAD_MAX_N:
+            raise ValueError(f'frames: plan {i} (row {row}): the padded crop of {n} is above {PAD_MAX_N}')
+        if h < 1 or w < 1 or rs < 0 or ps < 0 or off < 0 or max(abs(t), abs(l), h, w, rs, ps) >= MAX_COORD or off + (h - 1) * rs + (w - 1) * ps + chans > head_bytes:
+            raise ValueError(f'frames: plan {i} (row {row}): the view (offset {off}, {h} x {w}, strides {rs}, {ps}) lies outside the packed head of '
+                             f'{head_bytes} bytes')
+        pads = [max(0, -t), max(0, -l), max(0, t + n - h), max(0, l + n - w)]
+        if pads != [pt, pl, pb, pr] or not any(pads):
+            raise ValueError(f'frames: plan {i} (row {row}): the pads {[pt, pl, pb, pr]} are not those of a box that leaves its view ({pads})')
+        if k != ((96 * n + 1500) // 1000) | 1:
+            raise ValueError(f'frames: plan {i} (row {row}): k {k} is not ((96 n + 1500) // 1000) | 1 for n {n}')
+        if ws < end or ws % PAD_ALIGN or ws + n * n * chans > buf_bytes:
+            raise ValueError(f'frames: plan {i} (row {row}): the workspace image at {ws} ({PAD_ALIGN}-byte aligned, behind the head and the images '
+                             f'before it) does not fit the buffer of {buf_bytes} bytes')
+        end = ws + n * n * chans
+
+
+def _blend(x, y, w):
+    """x + (y - x) w; a weight of exactly 0 returns x, of exactly 1 returns y"""
+    return torch.where(w <= 0, x, torch.where(w >= 1, y, x + (y - x) * w))
+
+
+def _side(n, p0, p1):
+    """1 - min(i / p0, (n - 1 - i) / p1) for i = 0 .. n - 1 in fp32; a term whose pad is 0 is +inf"""
+    i = torch.arange(n, dtype=torch.float32)
+    inf = torch.full((n,), float('inf'), dtype=torch.float32)
+    u = i / torch.tensor(float(p0), dtype=torch.float32) if p0 else inf
+    v = (n - 1 - i) / torch.tensor(float(p1), dtype=torch.float32) if p1 else inf
+    return 1.0 - torch.minimum(u, v)
+
+
+def _pad_view(buf, p, g):
+    """one plan row -> uint8 [n, n, C]: the definition of csrc/frames_pad.hip in fp32 torch ops"""
+    _, view, off, h, w, rs, ps, t, l, n, pt, pl, pb, pr, k, _ = p
+    chans, mask = (1, True) if view else (3, False)
+    crop = _crop(buf, off, h, w, rs, ps, chans, t, l, n, mask)
+    radius = (k - 1) // 2
+    index = _reflect101(torch.arange(-radius, n + radius, dtype=torch.int64), n)
+    ext = crop[:, :, index]
+    mid = torch.zeros_like(crop)
+    for q in range(k):
+        mid = mid + ext[:, :, q:q + n] * g[q]
+    ext = mid[:, index, :]
+    blur = torch.zeros_like(crop)
+    for q in range(k):
+        blur = blur + ext[:, q:q + n, :] * g[q]
+    mh, mv = _side(n, pl, pr)[None, :], _side(n, pt, pb)[:, None]
+    m = torch.maximum(mh, mv)
+    a = (3.0 * m + 1.0).clamp(0.0, 1.0)
+    f = (mh.expand(n, n) if mask else m).clamp(0.0, 1.0)
+    if mask:
+        fade = torch.zeros(1, 1, 1, dtype=torch.float32)
+    else:
+        v = crop.reshape(chans, -1).sort(dim=1).values
+        fade = ((v[:, (n * n - 1) // 2] + v[:, (n * n) // 2]) / 2.0)[:, None, None]
+    y = _blend(_blend(crop, blur, a[None]), fade.expand_as(crop), f[None])
+    return y.round().clamp(0.0, 255.0).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+
+def pad_host(buf, table, size):
+    """``pad_plan`` and ``hipops.frames_pad`` for CPU tensors -> (buffer of the plan's total size: ``buf``, then the workspace images; rewritten table)"""
+    if not (torch.is_tensor(buf) and buf.dtype == torch.uint8 and buf.dim() == 1 and not buf.is_cuda):
+        raise ValueError('frames.pad_host: buf must be a 1-D uint8 CPU tensor')
+    table2, plan, weights, total = pad_plan(table, buf.numel(), size)
+    out = torch.zeros(total, dtype=torch.uint8)
+    out[:buf.numel()] = buf
+    for p, g in zip(plan.tolist(), weights):
+        n, chans, ws = p[9], 1 if p[1] else 3, p[15]
+        out[ws:ws + n * n * chans] = _pad_view(buf, p, g).reshape(-1)
+    return out, table2
+
+
+def prepare_host(buf, table, size, blur_padded_bands=False):
+    """``hipops.frames_prepare`` for CPU tensors: (image, mask, product), fp32 [slots, 3, size, size] each, None where no row asks;
+    ``blur_padded_bands``: through ``pad_host`` first"""
     if not (torch.is_tensor(buf) and buf.dtype == torch.uint8 and buf.dim() == 1 and not buf.is_cuda):
         raise ValueError('frames.prepare_host: buf must be a 1-D uint8 CPU tensor')
+    if blur_padded_bands:
+        buf, table = pad_host(buf, table, size)
     counts = check_table(table, buf.numel(), size)
     outs = [torch.empty(c, 3, size, size, dtype=torch.float32) if c else None for c in counts]
     for r in table.tolist():
@@ -222,24 +362,34 @@ def note_padding(table):
             _deviation_logged = True
             logger.warning('a bounding box leaves its frame by more than 2 pixels: the padded band carries the border rule\'s pixels as they are '
                            '(reflected image, replicated mask); the reference also blurs the band and fades it to the median colour '
-                           '(crop_with_padding), which is not provided')
+                           '(crop_with_padding): pass --blur_padded_bands for that')
             return
 
 
-def prepare(raw_batch, size, device):
+def prepare(raw_batch, size, device, blur_padded_bands=False):
     """a raw batch (module docstring) -> the standard (data_dict, target_dict), fp32 on ``device``: ``enc_rgbs`` B x K x 3 x S x S,
     ``pose_input_rgbs``, ``target_rgbs`` B x 1 x 3 x S x S, ``real_segm`` B x 1 x 3 x S x S, ``label`` -- whichever the rows of the table write.
-    On a GPU: one pinned host-to-device copy of the packed bytes, then one launch on the current stream."""
+    On a GPU: one pinned host-to-device copy of the packed bytes, then one launch on the current stream.  ``blur_padded_bands``: a batch with a box
+    that leaves its view gets ONE device buffer of the plan's total size, the pinned bytes copied into its head, the pad launches
+    (``hipops.frames_pad``) and then the same one launch on the rewritten table."""
     buf, table, label = raw_batch['buf'], raw_batch['table'], raw_batch['label']
     device = torch.device(device)
-    note_padding(table)
+    if not blur_padded_bands:
+        note_padding(table)
     if device.type == 'cuda':
         from latent_pose_reenactment_amd import hipops
         if not buf.is_pinned():
             buf = buf.pin_memory()
-        image, mask, product = hipops.frames_prepare(buf.to(device, non_blocking=True), table, size)
+        plan = pad_plan(table, buf.numel(), size) if blur_padded_bands else None
+        if plan is not None and plan[1].shape[0]:
+            table, rows, weights, total = plan
+            dev = torch.empty(total, dtype=torch.uint8, device=device)
+            dev[:buf.numel()].copy_(buf, non_blocking=True)
+            image, mask, product = hipops.frames_prepare(hipops.frames_pad(dev, buf.numel(), rows, weights), table, size)
+        else:
+            image, mask, product = hipops.frames_prepare(buf.to(device, non_blocking=True), table, size)
     else:
-        image, mask, product = prepare_host(buf, table, size)
+        image, mask, product = prepare_host(buf, table, size, blur_padded_bands)
     b, k = label.shape[0], int(raw_batch['frames'])
     data_dict, target_dict = {}, {}
     if k == 0:                  # fine-tuning: the one image is encoder input and pose input alike (:200-202)

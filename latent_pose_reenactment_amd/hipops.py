@@ -1373,6 +1373,32 @@ def frames_prepare(buf: Tensor, table: Tensor, size: int):
     return tuple(outs)
 
 
+def frames_pad(buf: Tensor, nbytes: int, plan: Tensor, weights: Tensor):
+    """fills the workspace images of a ``frames.pad_plan`` in place (the definition: the header comment of csrc/frames_pad.hip) and returns ``buf``:
+    ``buf`` = uint8 on the device, at least the plan's total size, its first ``nbytes`` the packed frames; ``plan`` int64 [P, 16] and ``weights``
+    fp32 [P, 100] on the HOST.  Each plan row's crop through the border rule, blurred in the padded bands, faded to the median colour (a mask: to 0)
+    and rounded, is written as a dense uint8 [n, n, C] image at its ``ws_off``; no other byte of ``buf`` changes.  The plan is checked here
+    (ValueError naming the plan row: a view outside the head, pads or k the box does not give, a workspace image outside the tail, a crop above 1024);
+    then a clear and three launches on the current stream (lp_frames_pad), bit-reproducible.  No gradient."""
+    from latent_pose_reenactment_amd import frames
+    if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous()):
+        raise ValueError('frames_pad: buf must be a contiguous 1-D uint8 tensor')
+    if not buf.is_cuda:
+        raise ValueError(f'frames_pad: buf is on {buf.device}: it must be a CUDA tensor (the host version is frames.pad_host)')
+    nbytes = int(nbytes)
+    frames.check_plan(plan, weights, nbytes, buf.numel())
+    plan, weights = plan.contiguous(), weights.contiguous()
+    plans = plan.shape[0]
+    with torch.cuda.device(buf.device):
+        plan_dev = (plan if plan.is_pinned() else plan.pin_memory()).to(buf.device, non_blocking=True)
+        weights_dev = (weights if weights.is_pinned() else weights.pin_memory()).to(buf.device, non_blocking=True)
+        hist = torch.empty(plans * 768, dtype=torch.int32, device=buf.device)
+        median = torch.empty(plans * 3, dtype=torch.float32, device=buf.device)
+        check(_lib.lib().lp_frames_pad(buf.data_ptr(), buf.numel(), nbytes, plan.data_ptr(), plan_dev.data_ptr(), plans, weights_dev.data_ptr(),
+                                       hist.data_ptr(), median.data_ptr(), _stream()), 'lp_frames_pad')
+    return buf
+
+
 VISUAL_SHEET_MAX_PANELS = 12
 
 
