@@ -580,7 +580,33 @@ int lp_frames_pad(unsigned char* buf, long long buf_bytes, long long head_bytes,
 int lp_visual_sheet(const float* const* panels, const long long* strides, const int* channels, int P, int N, int H, int W,
                     const unsigned char* caption, int Hc, unsigned char* out, void* stream);
 
-/* ---- fused multi-tensor optimizers + EMA (runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
+/* (additive, ABI 12) Baseline JPEG encoder of the drive output (csrc/jpeg.hip holds the definition: JFIF, 4:4:4, the Annex K tables, one restart
+ * interval per MCU row).  rows = ceil(H / 8), mcus = ceil(W / 8).
+ * lp_jpeg_transform: frames = DEVICE uint8, logical [T][H][W][3] RGB read through strides = HOST array of 4 element strides (frame, row, column,
+ * channel), read at call time; qtables = HOST uint8 [2][64] in natural (row-major) order, each 1 .. 255, read at call time and passed to the
+ * kernel by value; coefs = DEVICE int16 [T][rows][mcus][3][64], the quantised coefficients in zigzag order.  ONE launch, no atomics, no workspace.
+ * lp_jpeg_entropy_size: coefs = ANY DEVICE int16 table of that shape, 16-byte aligned (values are clamped to -1023 .. 1023, DC -1024 .. 1023);
+ * scratch = DEVICE, 16-byte aligned, at least lp_jpeg_entropy_scratch_bytes(T, rows, mcus) bytes, contents irrelevant on entry; header_bytes =
+ * the length of the frame header every file starts with; offsets = DEVICE int64 [T + 1], written: file t will occupy bytes offsets[t] ..
+ * offsets[t + 1], offsets[T] is the size of the output.  Four launches (integer atomicOr only: the bytes do not depend on the order of arrival).
+ * lp_jpeg_entropy_write: the same scratch and geometry, header = DEVICE uint8 [header_bytes] (utils/mjpeg.jpeg_header), out = DEVICE uint8
+ * [out_bytes] with out_bytes = offsets[T]: writes every file -- header, stuffed scan, RST markers, EOI.  ONE launch; every store is checked
+ * against out_bytes.  Neither call allocates or synchronises: the caller reads offsets[T] between the two.
+ * lp_jpeg_code_table: the coder's Huffman codes by symbol, (code << 5) | length, into a HOST array of 2 x 12 (DC) + 2 x 256 (AC) words; returns
+ * that count.  No device work.
+ * LP_ERR_ARG: null pointer, T, H, W, rows or mcus < 1, H or W above 65535, a table entry of 0, a misaligned or short scratch, header_bytes outside
+ * 0 .. 65536, out_bytes < 1; LP_ERR_UNSUPPORTED: a grid beyond one launch or a scratch beyond 2^31 - 1 bytes (lp_jpeg_entropy_scratch_bytes
+ * returns the negative code) -- all checked before any device work. */
+int lp_jpeg_transform(const unsigned char* frames, const long long* strides, int T, int H, int W, const unsigned char* qtables, short* coefs,
+                      void* stream);
+long long lp_jpeg_entropy_scratch_bytes(int T, int rows, int mcus);
+int lp_jpeg_entropy_size(const short* coefs, int T, int rows, int mcus, int header_bytes, void* scratch, long long scratch_bytes,
+                         long long* offsets, void* stream);
+int lp_jpeg_entropy_write(const void* scratch, long long scratch_bytes, int T, int rows, int mcus, const unsigned char* header,
+                          int header_bytes, unsigned char* out, long long out_bytes, void* stream);
+int lp_jpeg_code_table(unsigned int* table);
+
+/* ---- fused multi-tensor optimizers + EMA(runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.
  * lp_mt_ema: p <- p*alpha + g*(1-alpha) (copy_only=1: p <- g, used for buffers). */

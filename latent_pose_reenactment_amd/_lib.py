@@ -115,6 +115,11 @@ SIGNATURES = {
     'lp_frames_prepare': (_i, [_vp, _ll, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'lp_frames_pad': (_i, [_vp, _ll, _ll, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'lp_visual_sheet': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'lp_jpeg_transform': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'lp_jpeg_entropy_scratch_bytes': (_ll, [_i, _i, _i]),
+    'lp_jpeg_entropy_size': (_i, [_vp, _i, _i, _i, _i, _vp, _ll, _vp, _vp]),
+    'lp_jpeg_entropy_write': (_i, [_vp, _ll, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
+    'lp_jpeg_code_table': (_i, [_vp]),
     'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

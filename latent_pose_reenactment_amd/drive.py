@@ -2,8 +2,9 @@
 """Reenactment ("driving") entry point with the reference's CLI (drive.py:19-98): load a fine-tuned checkpoint, take the
 EMA weights, and for every driving frame run ``embedder.get_pose_embedding`` + ``generator`` (HIP kernels, eval mode: the
 spectral norms are constant so the packed bf16 weights are reused).  The reference writes an .mp4 through cv2 (absent here,
-out of scope): frames are written as one .npy uint8 array [T, H, 2W, 3] (driver | result) per driving sequence instead, or with
-``--format png`` as one PNG per frame, <destination>/<driver>/<frame:06>.png (PIL)."""
+out of scope): frames are written as one .npy uint8 array [T, H, 2W, 3] (driver | result) per driving sequence instead, with
+``--format png`` as one PNG per frame, <destination>/<driver>/<frame:06>.png (PIL), or with ``--format avi`` as a playable Motion-JPEG video
+<destination>/<driver>.avi whose frames are JPEG-encoded on the GPU (``hipops.jpeg_encode``): only the compressed bytes cross PCIe."""
 import argparse
 import copy
 import logging
@@ -84,6 +85,25 @@ def write_png_frames(directory, video):
     return paths
 
 
+AVI_CHUNK = 64          # frames per hipops.jpeg_encode call
+
+
+def write_avi(path, video, fps=25, quality=90, chunk=AVI_CHUNK):
+    """``video``: uint8 [T, H, W, 3] frame grids, on the device as ``drive_frames`` leaves them -> a Motion-JPEG AVI at ``path``.  The frames are
+    encoded where they are, ``chunk`` at a time (csrc/jpeg.hip; one read-back of one integer per chunk), and only the compressed bytes are copied to
+    the host, where utils/mjpeg.AviWriter puts them into the container.  Returns the number of bytes written"""
+    from latent_pose_reenactment_amd import hipops
+    from latent_pose_reenactment_amd.utils.mjpeg import AviWriter
+    if not (isinstance(video, torch.Tensor) and video.dtype == torch.uint8 and video.dim() == 4 and video.shape[3] == 3 and video.shape[0] >= 1):
+        raise ValueError(f'write_avi: video must be a uint8 tensor [T, H, W, 3] with T >= 1, got '
+                         f'{(video.dtype, tuple(video.shape)) if isinstance(video, torch.Tensor) else type(video).__name__}')
+    chunk = max(1, int(chunk))
+    with AviWriter(path, video.shape[1], video.shape[2], fps) as avi:
+        for t in range(0, video.shape[0], chunk):
+            avi.add(*hipops.jpeg_encode(video[t:t + chunk], quality))
+    return os.path.getsize(path)
+
+
 def main():
     logging.basicConfig(level=logging.INFO, stream=sys.stdout, format="%(asctime)s - %(levelname)s - %(message)s")
     logger = logging.getLogger('drive')
@@ -94,8 +114,11 @@ def main():
     ap.add_argument('--images_paths', type=Path, nargs='+')
     ap.add_argument('--destination', type=Path, required=True)
     ap.add_argument('--batch_size', type=int, default=1, help='driving frames per generator call (the reference drives one frame at a time)')
-    ap.add_argument('--format', choices=('npy', 'png'), default='npy',
-                    help='npy: one uint8 array [T, H, 2W, 3] per driving sequence; png: the same frames as <destination>/<driver>/<frame:06>.png')
+    ap.add_argument('--format', choices=('npy', 'png', 'avi'), default='npy',
+                    help='npy: one uint8 array [T, H, 2W, 3] per driving sequence; png: the same frames as <destination>/<driver>/<frame:06>.png;\n'
+                         'avi: the same frames as a Motion-JPEG video <destination>/<driver>.avi, encoded on the GPU')
+    ap.add_argument('--fps', type=float, default=25, help='frame rate written into the .avi')
+    ap.add_argument('--jpeg_quality', type=int, default=90, help='JPEG quality of the .avi frames, 1 .. 100 (the IJG scale)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('drive.py needs the MI355X: the generator has no CPU fallback')
@@ -112,6 +135,11 @@ def main():
         for data_dict, _ in loader:
             utils.dict_to_device(data_dict, device)
             frames.append(drive_frames(embedder, generator, data_dict))       # uint8 on the device: nothing waits for the GPU here
+        if args.format == 'avi':
+            out = out.with_suffix('.avi')
+            nbytes = write_avi(out, torch.cat(frames), args.fps, args.jpeg_quality)       # the frames stay on the device
+            logger.info(f'wrote {sum(len(f) for f in frames)} frames ({nbytes} bytes) to {out}')
+            continue
         video = torch.cat(frames).cpu().numpy()                             # one device-to-host transfer (and sync) per sequence
         if args.format == 'png':
             out = out.with_suffix('')

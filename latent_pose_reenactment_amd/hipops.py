@@ -1484,6 +1484,199 @@ def visual_sheet(panels, caption: Optional[Tensor] = None, out: Optional[Tensor]
     return out
 
 
+# ---- baseline JPEG of the drive output (csrc/jpeg.hip holds the definition) ------------------------------------------------------------------------
+def _jpeg_refusal(rc, what):
+    """the C ABI's refusals of an argument (checked before any device work) surface as ValueError; anything else as LpError"""
+    if rc in (-1, -2):
+        msg = _lib.lib().lp_last_error()
+        raise ValueError(msg.decode() if msg else what)
+    check(rc, what)
+
+
+def _jpeg_frames(frames, who):
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f'{who}: frames must be a tensor, got {type(frames).__name__}')
+    if frames.dtype != torch.uint8:
+        raise ValueError(f'{who}: frames must be uint8, got {frames.dtype}')
+    if frames.dim() != 4:
+        raise ValueError(f'{who}: frames must be 4-D [T, H, W, 3], got shape {tuple(frames.shape)}')
+    if frames.shape[3] != 3:
+        raise ValueError(f'{who}: frames must be RGB [T, H, W, 3], got C = {frames.shape[3]}')
+    t, h, w, _ = frames.shape
+    if t < 1 or h < 1 or w < 1:
+        raise ValueError(f'{who}: empty input {tuple(frames.shape)}: T, H and W must be >= 1')
+    if h > 65535 or w > 65535:
+        raise ValueError(f'{who}: H and W must be <= 65535 (a JPEG frame header holds them in 16 bits), got {h} x {w}')
+    return t, h, w
+
+
+def _jpeg_coefs(coefs, who):
+    if not (isinstance(coefs, torch.Tensor) and coefs.dtype == torch.int16 and coefs.dim() == 5 and tuple(coefs.shape[3:]) == (3, 64)):
+        raise ValueError(f'{who}: coefs must be an int16 tensor [T, rows, mcus, 3, 64], got '
+                         f'{(coefs.dtype, tuple(coefs.shape)) if isinstance(coefs, torch.Tensor) else type(coefs).__name__}')
+    t, rows, mcus = coefs.shape[:3]
+    if t < 1 or rows < 1 or mcus < 1:
+        raise ValueError(f'{who}: empty coefficient table {tuple(coefs.shape)}')
+    return t, rows, mcus
+
+
+def jpeg_transform_host(frames: Tensor, quality: int = 90) -> Tensor:
+    """the quantised coefficients of csrc/jpeg.hip in torch ops on the frames' own device: int16 [T, rows, mcus, 3, 64] in zigzag order"""
+    from .utils import mjpeg
+    t, h, w = _jpeg_frames(frames, 'jpeg_transform_host')
+    rows, mcus = (h + 7) // 8, (w + 7) // 8
+    dev = frames.device
+    q = torch.from_numpy(mjpeg.quant_tables(quality).astype('float32')).to(dev)[[0, 1, 1]]          # [3, 64]
+    ys = torch.arange(8 * rows, device=dev).clamp(max=h - 1)
+    xs = torch.arange(8 * mcus, device=dev).clamp(max=w - 1)
+    rgb = frames.detach()[:, ys][:, :, xs].to(torch.float32)
+    R, G, B = rgb[..., 0], rgb[..., 1], rgb[..., 2]
+    planes = torch.stack((0.299 * R + 0.587 * G + 0.114 * B - 128.0, -0.168736 * R - 0.331264 * G + 0.5 * B,
+                          0.5 * R - 0.418688 * G - 0.081312 * B), dim=1)                                 # [T, 3, 8 rows, 8 mcus]
+    k = torch.arange(8, dtype=torch.float64)
+    basis = torch.cos((2 * k[None, :] + 1) * k[:, None] * torch.pi / 16) * 0.5
+    basis[0] = 0.125 ** 0.5
+    basis = basis.to(torch.float32).to(dev)
+    x = planes.reshape(t, 3, rows, 8, mcus, 8)
+    d = torch.einsum('vn,tcrymn->tcrymv', basis, x)                    # rows first
+    d = torch.einsum('uy,tcrymv->tcrumv', basis, d)                    # then columns
+    d = d.permute(0, 2, 4, 1, 3, 5).reshape(t, rows, mcus, 3, 64)
+    kq = torch.round(d / q)                                            # ties to even
+    lo = torch.full((64,), -1023.0, device=dev)
+    lo[0] = -1024.0
+    kq = torch.maximum(torch.minimum(kq, torch.tensor(1023.0, device=dev)), lo)
+    return kq[..., list(mjpeg.ZIGZAG)].to(torch.int16).contiguous()
+
+
+def jpeg_entropy_host(coefs: Tensor, header: bytes):
+    """the scan of csrc/jpeg.hip in numpy and Python integers: ``coefs`` int16 [T, rows, mcus, 3, 64] (any values: clamped as the definition
+    says) -> (uint8 [total], int64 [T + 1]) on the CPU, every frame = ``header`` + scan + EOI"""
+    import numpy as np
+    from .utils import mjpeg
+    t, rows, mcus = _jpeg_coefs(coefs, 'jpeg_entropy_host')
+    c = coefs.detach().cpu().numpy().astype(np.int64)
+    c[..., 1:] = np.clip(c[..., 1:], -1023, 1023)
+    c[..., 0] = np.clip(c[..., 0], -1024, 1023)
+    dc = [mjpeg.huffman_codes(mjpeg.DC_LUMA), mjpeg.huffman_codes(mjpeg.DC_CHROMA)]
+    ac = [mjpeg.huffman_codes(mjpeg.AC_LUMA), mjpeg.huffman_codes(mjpeg.AC_CHROMA)]
+
+    def extra(v, size):
+        return (v if v >= 0 else v - 1) & ((1 << size) - 1)
+
+    out, offsets = bytearray(), [0]
+    for f in range(t):
+        out += header
+        for r in range(rows):
+            acc, nbits, pred = 0, 0, [0, 0, 0]
+            for m in range(mcus):
+                for comp in range(3):
+                    blk, tab = c[f, r, m, comp], int(comp > 0)
+                    diff = int(blk[0]) - pred[comp]
+                    pred[comp] = int(blk[0])
+                    cat = abs(diff).bit_length()
+                    code, length = dc[tab][cat]
+                    acc, nbits = (((acc << length) | code) << cat) | extra(diff, cat), nbits + length + cat
+                    last = 0
+                    for k in np.flatnonzero(blk[1:]) + 1:
+                        k, v, run = int(k), int(blk[k]), int(k) - last - 1
+                        while run >= 16:
+                            code, length = ac[tab][0xF0]
+                            acc, nbits, run = (acc << length) | code, nbits + length, run - 16
+                        size = abs(v).bit_length()
+                        code, length = ac[tab][run << 4 | size]
+                        acc, nbits = (((acc << length) | code) << size) | extra(v, size), nbits + length + size
+                        last = k
+                    if last != 63:
+                        code, length = ac[tab][0x00]
+                        acc, nbits = (acc << length) | code, nbits + length
+            pad = -nbits % 8
+            acc, nbits = (acc << pad) | ((1 << pad) - 1), nbits + pad
+            out += acc.to_bytes(nbits // 8, 'big').replace(b'\xff', b'\xff\x00')
+            out += bytes((0xFF, 0xD0 + r % 8)) if r < rows - 1 else b'\xff\xd9'
+        offsets.append(len(out))
+    return torch.frombuffer(out, dtype=torch.uint8).clone(), torch.tensor(offsets, dtype=torch.int64)
+
+
+def jpeg_encode_host(frames: Optional[Tensor] = None, quality: int = 90, *, coefs: Optional[Tensor] = None):
+    """``jpeg_encode`` in torch and numpy ops, on the CPU.  ``coefs`` (int16 [T, rows, mcus, 3, 64]) in place of ``frames`` encodes a chosen
+    coefficient table as frames of 8 rows x 8 mcus pixels (the tests' way to the coder)"""
+    from .utils import mjpeg
+    quality = mjpeg.check_quality(quality, 'jpeg_encode_host')
+    if coefs is None:
+        _, h, w = _jpeg_frames(frames, 'jpeg_encode_host')
+        coefs = jpeg_transform_host(frames, quality)
+    else:
+        _, rows, mcus = _jpeg_coefs(coefs, 'jpeg_encode_host')
+        h, w = 8 * rows, 8 * mcus
+    return jpeg_entropy_host(coefs, mjpeg.jpeg_header(h, w, quality))
+
+
+def jpeg_transform(frames: Tensor, quality: int = 90) -> Tensor:
+    """int16 [T, rows, mcus, 3, 64]: the quantised DCT coefficients of uint8 RGB ``frames`` [T, H, W, 3] in zigzag order (the header comment of
+    csrc/jpeg.hip), ``frames`` read in place through its four strides.  The tables come from ``utils.mjpeg.quant_tables(quality)``, the integers of
+    the DQT segments.  ONE launch on the current stream (lp_jpeg_transform), no atomics.  CPU frames: ``jpeg_transform_host``."""
+    from .utils import mjpeg
+    t, h, w = _jpeg_frames(frames, 'jpeg_transform')
+    quality = mjpeg.check_quality(quality, 'jpeg_transform')
+    if not frames.is_cuda:
+        return jpeg_transform_host(frames, quality)
+    import ctypes
+    frames = frames.detach()
+    qt = mjpeg.quant_tables(quality)
+    strides = (ctypes.c_longlong * 4)(*frames.stride())
+    rows, mcus = (h + 7) // 8, (w + 7) // 8
+    with torch.cuda.device(frames.device):
+        coefs = torch.empty((t, rows, mcus, 3, 64), dtype=torch.int16, device=frames.device)
+        npix = t * rows * mcus * 64
+        with _Timed('jpeg_transform', 2.0 * npix * 3 * (5 + 16), (t, h, w), (3 * t * h * w, 6 * npix)):
+            _jpeg_refusal(_lib.lib().lp_jpeg_transform(frames.data_ptr(), ctypes.addressof(strides), t, h, w, qt.ctypes.data, coefs.data_ptr(),
+                                                       _stream()), 'lp_jpeg_transform')
+    return coefs
+
+
+def jpeg_entropy(coefs: Tensor, header: bytes):
+    """(uint8 [total], int64 [T + 1]) on the coefficients' device: every frame of ``coefs`` (int16 [T, rows, mcus, 3, 64], any values) as
+    ``header`` + the Huffman-coded scan with its restart markers + EOI, back to back (the header comment of csrc/jpeg.hip).  Four launches
+    (lp_jpeg_entropy_size), ONE device-to-host copy of one integer -- the total size --, one launch (lp_jpeg_entropy_write) into an output
+    allocated at exactly that size.  Bit-identical from run to run.  CPU coefficients: ``jpeg_entropy_host``."""
+    t, rows, mcus = _jpeg_coefs(coefs, 'jpeg_entropy')
+    header = bytes(header)
+    if not coefs.is_cuda:
+        return jpeg_entropy_host(coefs, header)
+    l = _lib.lib()
+    need = l.lp_jpeg_entropy_scratch_bytes(t, rows, mcus)
+    if need < 0:
+        _jpeg_refusal(int(need), 'lp_jpeg_entropy_scratch_bytes')
+    coefs = coefs.detach().contiguous()
+    dev = coefs.device
+    with torch.cuda.device(dev):
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(t + 1, dtype=torch.int64, device=dev)
+        head = torch.frombuffer(bytearray(header), dtype=torch.uint8).to(dev, non_blocking=True)
+        with _Timed('jpeg_entropy_size', 0.0, (t, rows, mcus), 2.0 * coefs.numel() * 2):
+            _jpeg_refusal(l.lp_jpeg_entropy_size(coefs.data_ptr(), t, rows, mcus, len(header), scratch.data_ptr(), need, offsets.data_ptr(),
+                                                 _stream()), 'lp_jpeg_entropy_size')
+        total = int(offsets[t].item())                                  # the one read-back
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        with _Timed('jpeg_entropy_write', 0.0, (t, rows, mcus), 2.0 * total):
+            _jpeg_refusal(l.lp_jpeg_entropy_write(scratch.data_ptr(), need, t, rows, mcus, head.data_ptr(), len(header), out.data_ptr(), total,
+                                                  _stream()), 'lp_jpeg_entropy_write')
+    return out, offsets
+
+
+def jpeg_encode(frames: Tensor, quality: int = 90):
+    """(uint8 [total], int64 [T + 1]) on the frames' device: uint8 RGB ``frames`` [T, H, W, 3] (any strides: what ``drive.drive_frames`` returns)
+    as T complete baseline JFIF files back to back, file t = bytes offsets[t] .. offsets[t + 1] (the header comment of csrc/jpeg.hip; 4:4:4, the
+    Annex K tables at ``quality`` 1 .. 100, one restart interval per block row).  ``jpeg_transform`` + ``jpeg_entropy``: six launches and one
+    read-back of one integer.  CPU frames: ``jpeg_encode_host``."""
+    from .utils import mjpeg
+    _, h, w = _jpeg_frames(frames, 'jpeg_encode')
+    quality = mjpeg.check_quality(quality, 'jpeg_encode')
+    if not frames.is_cuda:
+        return jpeg_encode_host(frames, quality)
+    return jpeg_entropy(jpeg_transform(frames, quality), mjpeg.jpeg_header(h, w, quality))
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)
