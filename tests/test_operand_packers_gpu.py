@@ -5,7 +5,8 @@ that decodes what these packers wrote, or requires another kernel to write "what
 Two identifications, and no other excuse for any element:
   * a NaN is compared by NaN-ness only (the payload is the hardware's);
   * in LOGICAL channels +0 and -0 are the same word (fmaxf(-0, +0) may return either).  Pad channels, rows and columns must be exactly 0x0000.
-Every 16-bit buffer a wrapper allocates is poisoned with 0x7fff (a NaN in both formats) before the kernel runs, so an unwritten word fails.
+Every 16-bit buffer a wrapper allocates is poisoned with 0x7fff (a NaN in both formats) before the kernel runs, so an unwritten word fails
+(tests/guarded_alloc.py, which also fences every such buffer and checks the fences after each test).
 
 Kept out of the bit-exact input sets, because their outcome rests on hardware modes nobody has measured on this part:
   * fp32 SUBNORMAL inputs (the denormal mode of the conversion instructions);
@@ -37,20 +38,11 @@ def _lib():
     return _lib.lib()
 
 
-@pytest.fixture(autouse=True)
-def poisoned_planes(monkeypatch):
-    """torch.empty / empty_like of int16 (what every wrapper allocates its planes with) return buffers full of 0x7fff while a test runs"""
-    real_empty, real_like = torch.empty, torch.empty_like
+from guarded_alloc import fence_fixture  # noqa: E402
 
-    def empty(*a, **k):
-        t = real_empty(*a, **k)
-        return t.fill_(POISON) if t.dtype == torch.int16 else t
-
-    def empty_like(*a, **k):
-        t = real_like(*a, **k)
-        return t.fill_(POISON) if t.dtype == torch.int16 else t
-    monkeypatch.setattr(torch, 'empty', empty)
-    monkeypatch.setattr(torch, 'empty_like', empty_like)
+# the shared harness (tests/guarded_alloc.py, fill A): every buffer a wrapper takes from torch.empty / empty_like is full of NaN-like words -- 0x7fff
+# in the int16 planes, as before -- and now also sits between two fences that are checked when the test is over
+poisoned_planes = fence_fixture('A')
 
 
 def test_the_poison_reaches_the_wrappers_buffers():

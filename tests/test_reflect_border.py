@@ -15,6 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
+import os as _os, sys as _sys
+_sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))
+from guarded_alloc import fence_fixture  # noqa: E402
+
+# every buffer a wrapper takes from torch.empty / empty_like while a test of this module runs is full of NaN-like words (guarded_alloc fill A) and sits
+# between two fences that are checked when the test is over; the assertions and tolerances below are what they were
+fenced_buffers = fence_fixture()
+
 CASES = [   # (N, H, W, Cin, Cout, upsample)
     (2, 4, 4, 16, 16, False), (3, 8, 8, 24, 40, False), (2, 8, 8, 16, 8, True), (8, 16, 16, 64, 64, False), (1, 4, 8, 8, 72, False),
     (9, 8, 4, 70, 12, False), (2, 32, 32, 32, 32, True), (2, 64, 64, 8, 8, False),

@@ -14,6 +14,14 @@ sys.path.insert(0, os.path.join(ROOT, 'latent_pose_reenactment_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 pytestmark = pytest.mark.gpu
 
+import os as _os, sys as _sys
+_sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))
+from guarded_alloc import fence_fixture  # noqa: E402
+
+# every buffer a wrapper takes from torch.empty / empty_like while a test of this module runs is full of NaN-like words (guarded_alloc fill A) and sits
+# between two fences that are checked when the test is over; the assertions and tolerances below are what they were
+fenced_buffers = fence_fixture()
+
 TOL = {0: 1e-2, 1: 3e-5, 2: 1e-3}
 
 
