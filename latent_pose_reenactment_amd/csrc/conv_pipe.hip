@@ -195,7 +195,9 @@ void conv_pipe_kernel(Conv16Params p) {
         }
     };
 
-    const int nch = p.CinP / 32;
+    // chunks of REAL channels (host: C8 % 32 == 0).  The pack pads CinP to a multiple of 64 with zero weights: a chunk at c0 >= C8 (Cin = 32, 96,
+    // 160, ...) would read the NEXT pixel's channels -- past the end of the planes at the last pixel -- and 0 x (a stale NaN / Inf pattern) is NaN
+    const int nch = p.C8 / 32;
     // ---- prologue: three taps of weights and the first halo; everything lands before the first fragment read
     issue_w(0, 0); issue_w(0, 1); issue_w(0, 2);
     issue_a(0, 0);

@@ -58,6 +58,8 @@ def pack_grouped(w, mode, prec):
 def act_pack(x, *, pro=0, scale=None, shift=None, prec=0, grad=False):
     if pro == 0:
         v = x
+    elif pro == 1:          # per-IMAGE affine [N, C] (AdaIN) + ReLU
+        v = torch.relu(x * scale[:, None, None, :] + shift[:, None, None, :])
     elif pro == 2:
         v = torch.relu(x)
     elif pro in (3, 4, 5):

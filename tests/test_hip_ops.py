@@ -187,7 +187,7 @@ def test_instnorm_stats(shape):
     ops = _ops()
     n, h, w, c = shape
     g = torch.Generator().manual_seed(3)
-    x = torch.randn(n, c, h, w, generator=g, dtype=torch.float64) * 3 + 10.0      # large mean: cancellation check
+    x = torch.randn(n, c, h, w, generator=g, dtype=torch.float64) * 3 + 10.0      # a mean of ~3 standard deviations: plain fp32 sums pass this too (ill-conditioned inputs: test_norm_conditioning_gpu.py)
     aff = torch.randn(n, 3 * c, generator=g, dtype=torch.float64)
     gamma, beta = aff[:, c:2 * c], aff[:, :c]
     mean = x.mean((2, 3)); var = x.var((2, 3), unbiased=False); rstd = 1 / torch.sqrt(var + 1e-4)
