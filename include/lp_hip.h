@@ -606,6 +606,34 @@ int lp_jpeg_entropy_write(const void* scratch, long long scratch_bytes, int T, i
                           int header_bytes, unsigned char* out, long long out_bytes, void* stream);
 int lp_jpeg_code_table(unsigned int* table);
 
+/* (additive, ABI 12) Baseline JPEG decoder of the image-folder loader (csrc/jpeg_decode.hip holds the definition: SOF0, 8 bits, grey / 4:4:4 /
+ * 4:2:2 / 4:2:0, integer IDCT, libjpeg's triangle upsampling, JFIF colour).  The tables are the ones utils/jpeg_parse.pack makes:
+ * frames = frames x 24 int64 (H, W, components, luma factors hmax, vmax, MCU columns and rows, restart interval, first coefficient block, plane
+ * offset, destination offset, first segment, segments, quantisation / DC / AC table of each component, 2 reserved), given twice: frames_host is
+ * read and checked at call time, frames_dev is the same table on the DEVICE; seg = segments x 4 int64 (frame, first byte, end byte, reserved),
+ * also given twice; a frame's segments are consecutive rows, one per restart interval.
+ * lp_jpeg_decode_entropy: scan = DEVICE uint8 [scan_bytes], the entropy-coded bytes without stuffing and markers; huffman = DEVICE int32
+ * [frames][8][96] (DC ids 0 .. 3, AC ids 0 .. 3; each maxcode[16], delta[16], 256 symbol bytes); coefs = DEVICE int16 [coef_blocks][64], 16-byte
+ * aligned: every block of every frame is written, in zigzag order; status = DEVICE int32 [frames]: 0 ok, 1 no code of <= 16 bits matches, 2 a run
+ * leaves the block, 3 the segment ends inside a code.  A clear of status and ONE launch, a lane per segment; every loop is bounded by header
+ * counts and every read is clamped to its segment: a corrupt stream ends with a status.
+ * lp_jpeg_decode_pixels: qtables = DEVICE uint8 [frames][4][64] in natural order; idct_host = HOST int32 [64], K[u][x] = rint(2^13 c(u) cos((2 x +
+ * 1) u pi / 16)), read at call time and passed to the kernel by value; planes = DEVICE uint8 [plane_bytes], workspace: on return it holds every
+ * frame's sample planes (luma, Cb, Cr over their whole block areas) at the frame's plane offset; out = DEVICE uint8 [out_bytes]: frame f is
+ * written as dense [H][W][3] RGB at its destination offset, no other byte of out is touched.  TWO launches (IDCT, upsampling + colour), no
+ * atomics, no floating point: bit-identical from run to run and independent of the other frames.
+ * Neither call allocates or synchronises: capturable.
+ * LP_ERR_ARG (naming the frame or segment): null pointer, misaligned coefs, counts < 1, H or W outside 1 .. 65535, MCU counts or segment counts
+ * that the header values do not give, a table id outside 0 .. 3, a segment outside scan or not among its frame's, blocks, planes or a destination
+ * outside their buffers, two frames whose segments, blocks, planes or destinations overlap, an IDCT entry outside -4096 .. 4096; LP_ERR_UNSUPPORTED: a sampling outside the four above, more than 65535 frames -- all
+ * checked before any device work. */
+int lp_jpeg_decode_entropy(const unsigned char* scan, long long scan_bytes, const long long* seg_host, const long long* seg_dev, int segments,
+                           const long long* frames_host, const long long* frames_dev, int frames, const int* huffman, short* coefs,
+                           long long coef_blocks, int* status, void* stream);
+int lp_jpeg_decode_pixels(const short* coefs, long long coef_blocks, const long long* frames_host, const long long* frames_dev, int frames,
+                          const unsigned char* qtables, const int* idct_host, unsigned char* planes, long long plane_bytes, unsigned char* out,
+                          long long out_bytes, void* stream);
+
 /* ---- fused multi-tensor optimizers + EMA(runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.

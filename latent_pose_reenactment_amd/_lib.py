@@ -120,6 +120,8 @@ SIGNATURES = {
     'lp_jpeg_entropy_size': (_i, [_vp, _i, _i, _i, _i, _vp, _ll, _vp, _vp]),
     'lp_jpeg_entropy_write': (_i, [_vp, _ll, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
     'lp_jpeg_code_table': (_i, [_vp]),
+    'lp_jpeg_decode_entropy': (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _vp, _vp]),
+    'lp_jpeg_decode_pixels': (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp, _vp, _ll, _vp, _ll, _vp]),
     'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -11,7 +11,10 @@ bytes and rebases the offsets; the loader returned by ``get_dataloader`` copies 
 and under ``--inference`` only what the reference loads then (fine-tuning form: enc_rgbs = pose_input_rgbs and the label; otherwise the encoder
 frames and the label).  Keypoints and stickmen (the FSTH family) are not read.  ``--blur_padded_bands`` (off by default) blurs the padded bands
 of a box that leaves its frame and fades them to the median colour, as the reference's ``crop_with_padding`` does (csrc/frames_pad.hip); without
-it they carry the border rule's pixels as they are (csrc/frames.hip)."""
+it they carry the border rule's pixels as they are (csrc/frames.hip).  ``--decode_jpeg_on_gpu`` (off by default) moves the JPEG decode to the device
+as well: the workers read the file bytes and parse the headers only (``utils.jpeg_parse``), the compressed scan crosses PCIe and is decoded into the
+same packed buffer (csrc/jpeg_decode.hip); a file outside the supported set, or a .png frame, is decoded with PIL in the worker as before; the
+masks stay with PIL."""
 import logging
 import random
 from itertools import chain
@@ -77,9 +80,10 @@ def get_part_data(args, part):
 class SampleLoader:
     """decoding only (voxceleb.SampleLoader.load_rgb / list_ids and this plugin's load_segm / bounding boxes in the reference)"""
 
-    def __init__(self, data_root, img_dir, segm_dir, bboxes_dir, deterministic):
+    def __init__(self, data_root, img_dir, segm_dir, bboxes_dir, deterministic, decode_jpeg_on_gpu=False):
         self.data_root, self.img_dir, self.segm_dir = Path(data_root), Path(img_dir), Path(segm_dir)
         self.deterministic = deterministic
+        self.decode_jpeg_on_gpu = decode_jpeg_on_gpu
         try:
             self.bboxes = np.load(bboxes_dir, allow_pickle=True).item()
         except (FileNotFoundError, IsADirectoryError):
@@ -106,10 +110,21 @@ class SampleLoader:
         return frames.scaled_square_box(l, t, r, b, SCALE)
 
     def load_rgb(self, path, i):
+        """-> H x W x 3 uint8; with ``decode_jpeg_on_gpu`` a ``jpeg_parse.Descriptor`` for a .jpg file of the supported set (its pixels are made on
+        the device) -- ValueError naming the file for a malformed one"""
         from PIL import Image
         img_path = self.data_root / self.img_dir / path / (i + '.jpg')
         if not img_path.exists():           # (lossless frames: what the tests write)
             img_path = img_path.with_suffix('.png')
+        if self.decode_jpeg_on_gpu and img_path.suffix == '.jpg':
+            from latent_pose_reenactment_amd.utils import jpeg_parse
+            data = img_path.read_bytes()
+            try:
+                descriptor = jpeg_parse.parse(data)
+            except ValueError as e:
+                raise ValueError(f'{img_path}: {e}') from e
+            if descriptor is not None:
+                return descriptor, str(img_path)
         with Image.open(img_path) as im:
             return np.array(im.convert('RGB'), dtype=np.uint8)          # (a copy: PIL's buffer is read-only)
 
@@ -145,6 +160,9 @@ class Dataset(torch.utils.data.Dataset):
         parser.add('--num_labels', type=int, default=98000, help='identities in the training split; set from the split when training from scratch')
         parser.add('--blur_padded_bands', default=False, action="store_bool",
                    help='blur the padded bands of a box that leaves its frame and fade them to the median colour (crop_with_padding)')
+        parser.add('--decode_jpeg_on_gpu', default=False, action="store_bool",
+                   help='decode the JPEG frames on the GPU: the workers parse the headers only and the compressed bytes cross PCIe (csrc/jpeg_decode.hip). '
+                        'Measured SLOWER per batch than the PIL decode on files without restart markers (README): it frees the workers, not time')
         return augmentation.get_args(parser)
 
     @staticmethod
@@ -157,7 +175,9 @@ class Dataset(torch.utils.data.Dataset):
 
     def __init__(self, args, part):
         self.dirlist = get_part_data(args, part)
-        self.loader = SampleLoader(args.data_root, args.img_dir, args.segm_dir, args.bboxes_dir, deterministic=part != 'train')
+        self.decode_jpeg_on_gpu = bool(getattr(args, 'decode_jpeg_on_gpu', False))
+        self.loader = SampleLoader(args.data_root, args.img_dir, args.segm_dir, args.bboxes_dir, deterministic=part != 'train',
+                                   decode_jpeg_on_gpu=self.decode_jpeg_on_gpu)
         self.inference = bool(getattr(args, 'inference', False))
         self.frames = args.n_frames_for_encoder
         self.size = args.image_size
@@ -168,20 +188,35 @@ class Dataset(torch.utils.data.Dataset):
 
     def __getitem__(self, index):
         """-> {'bytes': the decoded frames of this sample, packed; 'rows': their table rows, offsets relative to 'bytes' and slots relative to the
-        sample (image slot k < K: encoder frame k, K: the pose image); 'label'; 'index'}"""
+        sample (image slot k < K: encoder frame k, K: the pose image); 'label'; 'index'}.  With ``--decode_jpeg_on_gpu`` the offsets of the rows
+        still describe the DECODED layout ('size' bytes), identical to the PIL route's, while 'bytes' holds only what was decoded here -- masks and
+        fallback frames, 'regions' int64 [n, 3] = (offset in the decoded layout, offset in 'bytes', length) -- and 'jpeg' the packed descriptors
+        of the other frames (``jpeg_parse.pack``, destination offsets in the decoded layout) with their 'files'"""
         row = self.dirlist.iloc[index]
         path = row['path']
         chunks, rows, offset = [], [], 0
+        regions, descriptors, destinations, files, held = [], [], [], [], 0
 
         def add(array):
-            nonlocal offset
+            nonlocal offset, held
             start = offset
             chunks.append(torch.from_numpy(array).reshape(-1))
+            regions.append([start, held, array.size])
             offset += array.size
+            held += array.size
             return start
 
         def image_columns(i):
+            nonlocal offset
             rgb = self.loader.load_rgb(path, i)
+            if isinstance(rgb, tuple):       # a descriptor: the pixels are decoded on the device into [offset, offset + H W 3)
+                descriptor, name = rgb
+                start, shape = offset, (descriptor.h, descriptor.w, 3)
+                descriptors.append(descriptor)
+                destinations.append(start)
+                files.append(name)
+                offset += descriptor.h * descriptor.w * 3
+                return frames.frame_rows(start, shape, self.loader.box(path, i), self.size)
             return frames.frame_rows(add(rgb), rgb.shape, self.loader.box(path, i), self.size)
 
         def mask_columns(i):
@@ -203,7 +238,13 @@ class Dataset(torch.utils.data.Dataset):
                 i = ids[-1]
                 rows.append(frames.make_row(image_columns(i), mask_columns(i), image_slot=self.frames, mask_slot=0, product_slot=0))
             label = int(self.dirlist.index[index])
-        return {'bytes': torch.cat(chunks), 'rows': torch.tensor(rows, dtype=torch.int64), 'label': label, 'index': int(index)}
+        sample = {'bytes': torch.cat(chunks) if chunks else torch.zeros(0, dtype=torch.uint8), 'rows': torch.tensor(rows, dtype=torch.int64),
+                  'label': label, 'index': int(index)}
+        if self.decode_jpeg_on_gpu:
+            from latent_pose_reenactment_amd.utils import jpeg_parse
+            sample.update(size=offset, regions=torch.tensor(regions, dtype=torch.int64).reshape(-1, 3), files=files,
+                          jpeg=jpeg_parse.pack(descriptors, destinations) if descriptors else None)
+        return sample
 
 
 _OFFSETS = [c for c, name in enumerate(frames.COLUMNS) if name.endswith('_off')]
@@ -230,10 +271,26 @@ class Collate:
             for col in (_MASK_SLOT, _PRODUCT_SLOT):
                 rows[:, col] = torch.where(rows[:, col] >= 0, torch.full_like(local, s), rows[:, col])
             tables.append(rows)
-            base += sample['bytes'].numel()
-        return {'buf': torch.cat([sample['bytes'] for sample in samples]), 'table': torch.cat(tables), 'frames': k, 'pose': self.pose,
-                'label': torch.tensor([sample['label'] for sample in samples], dtype=torch.int64),
-                'index': torch.tensor([sample['index'] for sample in samples], dtype=torch.int64)}
+            base += sample['size'] if 'size' in sample else sample['bytes'].numel()
+        raw = {'buf': torch.cat([sample['bytes'] for sample in samples]), 'table': torch.cat(tables), 'frames': k, 'pose': self.pose,
+               'label': torch.tensor([sample['label'] for sample in samples], dtype=torch.int64),
+               'index': torch.tensor([sample['index'] for sample in samples], dtype=torch.int64)}
+        if 'size' in samples[0]:             # --decode_jpeg_on_gpu: 'buf' holds the regions decoded in the worker, 'jpeg' the segments of the rest
+            from latent_pose_reenactment_amd.utils import jpeg_parse
+            regions, packs, bases, files, base, held = [], [], [], [], 0, 0
+            for sample in samples:
+                regions.append(sample['regions'] + torch.tensor([base, held, 0], dtype=torch.int64))
+                if sample['jpeg'] is not None:
+                    packs.append(sample['jpeg'])
+                    bases.append(base)
+                    files += sample['files']
+                base += sample['size']
+                held += sample['bytes'].numel()
+            jpeg = None
+            if packs:
+                jpeg = {key: torch.from_numpy(v) if isinstance(v, np.ndarray) else v for key, v in jpeg_parse.merge(packs, bases).items()}
+            raw.update(nbytes=base, regions=torch.cat(regions), jpeg=jpeg, files=files)
+        return raw
 
 
 class FrameLoader:
@@ -246,6 +303,7 @@ class FrameLoader:
         self.loader, self.dataset = loader, loader.dataset
         self.size, self.part = args.image_size, part
         self.blur_padded_bands = bool(getattr(args, 'blur_padded_bands', False))
+        self.pending = []                # decode status words on their way to the host (frames.prepare), checked before the next batch is asked for
         device = str(getattr(args, 'device', 'cuda'))
         self.device = device if device.startswith('cuda') and torch.cuda.is_available() else 'cpu'
         self.augmenter = augmentation.ParametricAugmenter(args)
@@ -279,10 +337,15 @@ class FrameLoader:
         return out
 
     def __iter__(self):
-        for raw in self.loader:
+        batches = iter(self.loader)
+        while True:
+            frames.check_decoded(self.pending)          # the batch before this one: a stream that did not decode raises, naming its file
+            raw = next(batches, None)
+            if raw is None:
+                return
             if not self.augmenter.is_empty():
                 raw = dict(raw, **self._aug_params(raw['index'].tolist()))
-            yield frames.prepare(raw, self.size, self.device, self.blur_padded_bands)
+            yield frames.prepare(raw, self.size, self.device, self.blur_padded_bands, pending=self.pending)
 
 
 def get_dataloader(args, part):

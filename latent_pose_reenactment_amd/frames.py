@@ -366,17 +366,85 @@ def note_padding(table):
             return
 
 
-def prepare(raw_batch, size, device, blur_padded_bands=False):
+STATUS_WORDS = {1: 'no Huffman code of <= 16 bits matches', 2: 'a run of zeros leaves its block', 3: 'a segment ends inside a code'}
+
+
+def check_decoded(pending):
+    """the decode status words ``_prepare_decoding`` sent on their way to pinned memory: waits for each copy's event, empties the list and raises
+    ValueError naming the first file whose stream did not decode"""
+    while pending:
+        status, event, files = pending.pop(0)
+        if event is not None:
+            event.synchronize()
+        bad = torch.nonzero(status).reshape(-1).tolist()
+        if bad:
+            pending.clear()
+            code = int(status[bad[0]])
+            raise ValueError(f'{files[bad[0]]}: the JPEG stream does not decode ({STATUS_WORDS.get(code, code)}; status {code}); '
+                             f'{len(bad)} of the {len(files)} JPEG frames of the batch are affected')
+
+
+def _prepare_decoding(raw_batch, size, device, blur_padded_bands, pending):
+    """``prepare`` for a raw batch of ``--decode_jpeg_on_gpu``: 'buf' holds only the regions the workers decoded (masks, fallback frames), 'regions'
+    int64 [n, 3] = (offset in the decoded layout, offset in 'buf', length), 'nbytes' the size of the decoded layout -- which the table describes,
+    identical to the PIL route's -- and 'jpeg' the packed segments of the other frames (``utils.jpeg_parse.merge``), 'files' their paths.
+    -> (image, mask, product).  On a GPU, in this order: ONE device buffer at the decoded size (the pad plan's total with ``blur_padded_bands``), the
+    regions copied into it from pinned memory, the decode launches (``hipops.jpeg_decode``) into the rest, then the existing launches; no host
+    synchronisation anywhere: the per-frame status goes to pinned memory with a non-blocking copy and is appended, with its event, to ``pending``
+    (``check_decoded``).  CPU: the same through ``hipops.jpeg_decode_host`` and ``prepare_host``, the status checked at once."""
+    from latent_pose_reenactment_amd import hipops
+    buf, table, nbytes, jpeg = raw_batch['buf'], raw_batch['table'], int(raw_batch['nbytes']), raw_batch['jpeg']
+    regions = []
+    for d, s, n in raw_batch['regions'].tolist():          # neighbours in both layouts (a mask behind its fallback frame, ...) travel as one copy
+        if regions and regions[-1][0] + regions[-1][2] == d and regions[-1][1] + regions[-1][2] == s:
+            regions[-1][2] += n
+        else:
+            regions.append([d, s, n])
+    if any(d < 0 or s < 0 or n < 0 or d + n > nbytes or s + n > buf.numel() for d, s, n in regions):
+        raise ValueError(f'frames: a region of the raw batch lies outside the decoded layout of {nbytes} bytes or the {buf.numel()} bytes held')
+    if device.type != 'cuda':
+        full = torch.zeros(nbytes, dtype=torch.uint8)
+        for d, s, n in regions:
+            full[d:d + n] = buf[s:s + n]
+        if jpeg is not None:
+            check_decoded([(hipops.jpeg_decode_host(jpeg, out=full).status, None, raw_batch['files'])])
+        return prepare_host(full, table, size, blur_padded_bands)
+    if not buf.is_pinned():
+        buf = buf.pin_memory()
+    plan = pad_plan(table, nbytes, size) if blur_padded_bands else None
+    padded = plan is not None and plan[1].shape[0]
+    dev = torch.empty(plan[3] if padded else nbytes, dtype=torch.uint8, device=device)
+    for d, s, n in regions:
+        dev[d:d + n].copy_(buf[s:s + n], non_blocking=True)
+    if jpeg is not None:
+        status = hipops.jpeg_decode(jpeg, out=dev).status
+        host = torch.empty(status.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        if pending is None:
+            check_decoded([(host, event, raw_batch['files'])])
+        else:
+            pending.append((host, event, raw_batch['files']))
+    if padded:
+        return hipops.frames_prepare(hipops.frames_pad(dev, nbytes, plan[1], plan[2]), plan[0], size)
+    return hipops.frames_prepare(dev, table, size)
+
+
+def prepare(raw_batch, size, device, blur_padded_bands=False, pending=None):
     """a raw batch (module docstring) -> the standard (data_dict, target_dict), fp32 on ``device``: ``enc_rgbs`` B x K x 3 x S x S,
     ``pose_input_rgbs``, ``target_rgbs`` B x 1 x 3 x S x S, ``real_segm`` B x 1 x 3 x S x S, ``label`` -- whichever the rows of the table write.
     On a GPU: one pinned host-to-device copy of the packed bytes, then one launch on the current stream.  ``blur_padded_bands``: a batch with a box
     that leaves its view gets ONE device buffer of the plan's total size, the pinned bytes copied into its head, the pad launches
-    (``hipops.frames_pad``) and then the same one launch on the rewritten table."""
+    (``hipops.frames_pad``) and then the same one launch on the rewritten table.  A batch of ``--decode_jpeg_on_gpu`` (it has 'jpeg'): see
+    ``_prepare_decoding``; ``pending`` is the caller's list for the status words (without one they are waited for and checked here)."""
     buf, table, label = raw_batch['buf'], raw_batch['table'], raw_batch['label']
     device = torch.device(device)
     if not blur_padded_bands:
         note_padding(table)
-    if device.type == 'cuda':
+    if 'jpeg' in raw_batch:
+        image, mask, product = _prepare_decoding(raw_batch, size, device, blur_padded_bands, pending)
+    elif device.type == 'cuda':
         from latent_pose_reenactment_amd import hipops
         if not buf.is_pinned():
             buf = buf.pin_memory()

@@ -1677,6 +1677,228 @@ def jpeg_encode(frames: Tensor, quality: int = 90):
     return jpeg_entropy(jpeg_transform(frames, quality), mjpeg.jpeg_header(h, w, quality))
 
 
+# ---- baseline JPEG decode of the loader's frames (csrc/jpeg_decode.hip holds the definition) ---------------------------------------------------------
+class JpegDecoded(NamedTuple):
+    """``buf`` uint8: frame f = dense [H, W, 3] RGB at ``offsets[f]``; ``status`` int32 [N] on the buffer's device (0 ok, 1 no code matches, 2 a run
+    leaves its block, 3 a segment ends inside a code); the workspaces: ``coefs`` int16 [blocks, 64] in zigzag and scan order, ``planes`` uint8 (every
+    frame's sample planes at its plane offset); ``frames`` the int64 [N, 24] table of the call (``utils.jpeg_parse.FRAME_COLUMNS``), on the host"""
+    buf: Tensor
+    offsets: Tensor
+    status: Tensor
+    coefs: Tensor
+    planes: Tensor
+    frames: Tensor
+
+
+def _jpeg_packed(frames, offsets, who):
+    """a list of ``utils.jpeg_parse.Descriptor`` or the packed form (``jpeg_parse.pack`` / ``merge``) -> the packed form as contiguous host tensors"""
+    import numpy as np
+    from .utils import jpeg_parse
+    if isinstance(frames, (list, tuple)):
+        if not frames or not all(isinstance(d, jpeg_parse.Descriptor) for d in frames):
+            raise ValueError(f'{who}: a non-empty list of jpeg_parse.Descriptor (or the packed form of jpeg_parse.pack) is expected')
+        if offsets is not None and len(offsets) != len(frames):
+            raise ValueError(f'{who}: {len(offsets)} offsets for {len(frames)} frames')
+        frames = jpeg_parse.pack(list(frames), None if offsets is None else [int(o) for o in offsets])
+    elif not isinstance(frames, dict) or any(k not in frames for k in ('scan', 'seg', 'frames', 'qt', 'huffman', 'coef_blocks', 'plane_bytes')):
+        raise ValueError(f'{who}: a list of jpeg_parse.Descriptor or the packed form of jpeg_parse.pack is expected, got {type(frames).__name__}')
+    elif offsets is not None:
+        raise ValueError(f'{who}: the packed form carries its destination offsets (column dst_off); offsets go with a list of descriptors')
+    pk = dict(frames)
+    for k, dt in (('scan', torch.uint8), ('seg', torch.int64), ('frames', torch.int64), ('qt', torch.uint8), ('huffman', torch.int32)):
+        t = pk[k] if isinstance(pk[k], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pk[k]))
+        if t.dtype != dt or t.is_cuda:
+            raise ValueError(f'{who}: the packed table {k!r} must be a HOST {dt} tensor, got {t.dtype} on {t.device}')
+        pk[k] = t.contiguous()
+    n = pk['frames'].shape[0]
+    if (pk['frames'].dim() != 2 or pk['frames'].shape[1] != jpeg_parse.NFRAME or n < 1 or pk['seg'].dim() != 2 or pk['seg'].shape[1] != jpeg_parse.NSEG
+            or tuple(pk['qt'].shape) != (n, 4, 64) or tuple(pk['huffman'].shape) != (n, 8, jpeg_parse.HUFF_WORDS) or pk['scan'].dim() != 1):
+        raise ValueError(f'{who}: the packed tables do not have the shapes of jpeg_parse.pack')
+    return pk
+
+
+def _jpeg_out(pk, out, device, who):
+    """the destination buffer: ``out`` as given, or a dense one of the packed form's size on ``device``"""
+    rows = pk['frames']
+    need = int((rows[:, 10] + rows[:, 0] * rows[:, 1] * 3).max())
+    if out is None:
+        if not pk.get('out_bytes'):
+            raise ValueError(f'{who}: destination offsets were given, so the buffer they point into (out) is needed too')
+        return torch.empty(int(pk['out_bytes']), dtype=torch.uint8, device=device), need
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError(f'{who}: out must be a contiguous 1-D uint8 tensor')
+    if int(rows[:, 10].min()) < 0 or need > out.numel():
+        bad = int(((rows[:, 10] < 0) | (rows[:, 10] + rows[:, 0] * rows[:, 1] * 3 > out.numel())).nonzero()[0])
+        raise ValueError(f'{who}: frame {bad}: the destination ({int(rows[bad, 0] * rows[bad, 1] * 3)} bytes at {int(rows[bad, 10])}) lies outside '
+                         f'the buffer of {out.numel()} bytes')
+    return out, need
+
+
+def jpeg_decode_host(frames, out: Optional[Tensor] = None, offsets=None) -> JpegDecoded:
+    """``jpeg_decode`` in numpy integers on the CPU: the definition of csrc/jpeg_decode.hip step for step, from the same packed tables the device
+    reads.  A frame whose stream does not decode gets its status; the other frames are not affected."""
+    import numpy as np
+    from .utils import jpeg_parse, mjpeg
+    pk = _jpeg_packed(frames, offsets, 'jpeg_decode_host')
+    buf, _ = _jpeg_out(pk, out, 'cpu', 'jpeg_decode_host')
+    if buf.is_cuda:
+        raise ValueError('jpeg_decode_host: out is on the GPU (the device version is jpeg_decode)')
+    rows, seg, scan = pk['frames'].tolist(), pk['seg'].tolist(), pk['scan'].numpy()
+    huff, qt = pk['huffman'].numpy(), pk['qt'].numpy().astype(np.int64)
+    n = len(rows)
+    coefs = np.zeros((int(pk['coef_blocks']), 64), dtype=np.int16)
+    planes = np.zeros(int(pk['plane_bytes']), dtype=np.uint8)
+    status = np.zeros(n, dtype=np.int32)
+    dst = buf.numpy()
+    K = jpeg_parse.idct_table().astype(np.int64).reshape(8, 8)
+    natural = np.array(mjpeg.ZIGZAG)
+    for f, r in enumerate(rows):
+        h, w, nc, hmax, vmax, mcux, mcuy, ri, coef_off, plane_off, dst_off, seg0, nseg = r[:13]
+        nluma = hmax * vmax if nc == 3 else 1
+        bpm = nluma + 2 if nc == 3 else 1
+        total = mcux * mcuy
+        tabs = [(t[:16].tolist(), t[16:32].tolist(), t[32:].view(np.uint8).tolist()) for t in huff[f]]
+        # entropy: a segment at a time, as a lane of the kernel walks it
+        for s in range(seg0, seg0 + nseg):
+            first = (s - seg0) * ri
+            count = min(ri, total - first) if ri else total
+            data = bytes(scan[seg[s][1]:seg[s][2]])
+            nbits = 8 * len(data)
+            big, width = int.from_bytes(data + bytes(8), 'big'), nbits + 64
+            used, st, pred = 0, 0, [0, 0, 0]
+
+            def symbol(tab):
+                nonlocal used
+                word = (big >> (width - used - 16)) & 0xFFFF
+                for l in range(16):
+                    code = word >> (15 - l)
+                    if code <= tab[0][l]:
+                        used += l + 1
+                        return tab[2][min(max(code + tab[1][l], 0), 255)]
+                return -1
+
+            def extend(size):
+                nonlocal used
+                v = (big >> (width - used - size)) & ((1 << size) - 1)
+                used += size
+                return v - (1 << size) + 1 if v < (1 << (size - 1)) else v
+
+            for b in range(count * bpm):
+                if st:
+                    break                   # (coefs starts as zeros: what the kernel writes behind a failure)
+                blk = coefs[coef_off + first * bpm + b]
+                j = b % bpm
+                c = 0 if j < nluma else j - nluma + 1
+                sd = symbol(tabs[r[16 + c]])
+                if sd < 0 or sd > 15:
+                    st = 1
+                    continue
+                diff = extend(sd) if sd else 0
+                if used > nbits:
+                    st = 3
+                    continue
+                pred[c] = ((pred[c] + diff + 32768) & 0xFFFF) - 32768
+                blk[0] = pred[c]
+                k = 1
+                for _ in range(63):
+                    if k >= 64:
+                        break
+                    rs = symbol(tabs[4 + r[19 + c]])
+                    if rs < 0:
+                        st = 1
+                        break
+                    run, size = rs >> 4, rs & 15
+                    if size == 0:
+                        if used > nbits:
+                            st = 3
+                            break
+                        if run != 15:
+                            break
+                        k += 16
+                        continue
+                    k += run
+                    if k > 63:
+                        st = 2
+                        break
+                    a = extend(size)
+                    if used > nbits:
+                        st = 3
+                        break
+                    blk[k] = a
+                    k += 1
+            status[f] = max(status[f], st)
+        # dequantise + IDCT, all blocks of the frame at once
+        blocks = total * bpm
+        comp = np.array([0 if j < nluma else j - nluma + 1 for j in range(bpm)] * total)
+        F = np.zeros((blocks, 64), dtype=np.int64)
+        F[:, natural] = coefs[coef_off:coef_off + blocks].astype(np.int64)
+        F = np.clip(F * qt[f][np.array(r[13:16])[comp]], -32768, 32767).reshape(blocks, 8, 8)
+        T = (np.einsum('ux,buv->bxv', K, F) + 512) >> 10
+        S = np.clip(((np.einsum('vy,bxv->bxy', K, T) + 32768) >> 16) + 128, 0, 255).astype(np.uint8).reshape(total, bpm, 8, 8)
+        ph0, pw0 = mcuy * (vmax if nc == 3 else 1) * 8, mcux * (hmax if nc == 3 else 1) * 8
+        luma = S[:, :nluma].reshape(mcuy, mcux, ph0 // (8 * mcuy), pw0 // (8 * mcux), 8, 8).transpose(0, 2, 4, 1, 3, 5).reshape(ph0, pw0)
+        planes[plane_off:plane_off + ph0 * pw0] = luma.reshape(-1)
+        rgb = [luma[:h, :w].astype(np.int64)] * 3
+        if nc == 3:
+            chroma = []
+            for c in (1, 2):
+                p = S[:, nluma + c - 1].reshape(mcuy, mcux, 8, 8).transpose(0, 2, 1, 3).reshape(mcuy * 8, mcux * 8)
+                at = plane_off + ph0 * pw0 + (c - 1) * p.size
+                planes[at:at + p.size] = p.reshape(-1)
+                x = p[:-(-h // vmax), :-(-w // hmax)].astype(np.int64)
+                if vmax == 2:               # replicated edges give the edge rules: 3 cs + cs = 4 cs
+                    x = np.stack([3 * x + np.concatenate([x[:1], x[:-1]]), 3 * x + np.concatenate([x[1:], x[-1:]])], axis=1).reshape(-1, x.shape[1])[:h]
+                if hmax == 2:
+                    lo, sh = (8, 4) if vmax == 2 else (1, 2)
+                    even = (3 * x + np.concatenate([x[:, :1], x[:, :-1]], axis=1) + lo) >> sh
+                    odd = (3 * x + np.concatenate([x[:, 1:], x[:, -1:]], axis=1) + lo + (1 if vmax == 1 else -1)) >> sh
+                    x = np.stack([even, odd], axis=2).reshape(x.shape[0], -1)[:, :w]
+                chroma.append(x - 128)
+            cb, cr = chroma
+            y = rgb[0]
+            rgb = [y + ((91881 * cr + 32768) >> 16), y + ((-22554 * cb - 46802 * cr + 32768) >> 16), y + ((116130 * cb + 32768) >> 16)]
+        dst[dst_off:dst_off + h * w * 3] = np.clip(np.stack(rgb, axis=2), 0, 255).astype(np.uint8).reshape(-1)
+    return JpegDecoded(buf, pk['frames'][:, 10].clone(), torch.from_numpy(status), torch.from_numpy(coefs), torch.from_numpy(planes), pk['frames'])
+
+
+def jpeg_decode(frames, out: Optional[Tensor] = None, offsets=None, device=None) -> JpegDecoded:
+    """JPEG files -> uint8 RGB on the device (the header comment of csrc/jpeg_decode.hip).  ``frames``: a list of ``utils.jpeg_parse.Descriptor``
+    (what ``jpeg_parse.parse`` returns for a supported file) or the packed form of ``jpeg_parse.pack`` / ``merge`` (the loader's collate function
+    makes it in the worker).  Frame f is written as dense [H, W, 3] at ``offsets[f]`` of ``out`` (a 1-D uint8 tensor; the packed form carries the
+    offsets in its table), no other byte of ``out`` changes; without ``out`` the frames are packed back to back into a new buffer on ``device``.
+    A clear and THREE launches on the current stream (lp_jpeg_decode_entropy, lp_jpeg_decode_pixels), the tables copied from pinned memory without
+    blocking; no host synchronisation: ``status`` stays on the device for the caller to read when it suits.  Arguments the C ABI refuses raise
+    ValueError naming the frame.  A CPU ``out`` (or ``device`` 'cpu'): ``jpeg_decode_host``."""
+    import ctypes
+    from .utils import jpeg_parse
+    device = torch.device(device if device is not None else (out.device if isinstance(out, torch.Tensor) else 'cuda'))
+    if device.type != 'cuda':
+        return jpeg_decode_host(frames, out, offsets)
+    pk = _jpeg_packed(frames, offsets, 'jpeg_decode')
+    if isinstance(out, torch.Tensor) and not out.is_cuda:
+        raise ValueError(f'jpeg_decode: out is on {out.device} and device is {device}')
+    n, nseg = pk['frames'].shape[0], pk['seg'].shape[0]
+    blocks, plane_bytes = int(pk['coef_blocks']), int(pk['plane_bytes'])
+    K = jpeg_parse.idct_table()
+    l = _lib.lib()
+    with torch.cuda.device(device):
+        buf, _ = _jpeg_out(pk, out, device, 'jpeg_decode')
+        dev = {k: (pk[k] if pk[k].is_pinned() else pk[k].pin_memory()).to(device, non_blocking=True) for k in ('scan', 'seg', 'frames', 'qt', 'huffman')}
+        coefs = torch.empty((max(blocks, 1), 64), dtype=torch.int16, device=device)
+        planes = torch.empty(max(plane_bytes, 1), dtype=torch.uint8, device=device)
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        with _Timed('jpeg_decode_entropy', 0.0, (n, nseg), (pk['scan'].numel(), 128 * blocks)):
+            _jpeg_refusal(l.lp_jpeg_decode_entropy(dev['scan'].data_ptr(), pk['scan'].numel(), pk['seg'].data_ptr(), dev['seg'].data_ptr(), nseg,
+                                                   pk['frames'].data_ptr(), dev['frames'].data_ptr(), n, dev['huffman'].data_ptr(), coefs.data_ptr(),
+                                                   blocks, status.data_ptr(), _stream()), 'lp_jpeg_decode_entropy')
+        npix = int((pk['frames'][:, 0] * pk['frames'][:, 1]).sum())
+        with _Timed('jpeg_decode_pixels', 0.0, (n, blocks), (128 * blocks + 2 * 64 * blocks, 64 * blocks + 3 * npix)):
+            _jpeg_refusal(l.lp_jpeg_decode_pixels(coefs.data_ptr(), blocks, pk['frames'].data_ptr(), dev['frames'].data_ptr(), n, dev['qt'].data_ptr(),
+                                                  K.ctypes.data_as(ctypes.c_void_p), planes.data_ptr(), plane_bytes, buf.data_ptr(), buf.numel(),
+                                                  _stream()), 'lp_jpeg_decode_pixels')
+    return JpegDecoded(buf, pk['frames'][:, 10].clone(), status, coefs, planes, pk['frames'])
+
+
 def relu_bwd(dA: Tensor, x: Tensor) -> Tensor:
     _chk(dA, 'dA'); _chk(x, 'x')
     dx = torch.empty_like(x)
