@@ -2,7 +2,6 @@
 // counted-vmcnt tap pipeline): the launch parameter block and the epilogue that turns a wave's accumulator block into the outputs.
 #pragma once
 #include "lp_common.h"
-#include <stdlib.h>
 
 struct Conv16Params {
     const uint16_t* a_hi; const uint16_t* a_lo; const uint16_t* w_hi; const uint16_t* w_lo;
@@ -51,7 +50,7 @@ __device__ __forceinline__ bool conv16_block(const Conv16Params& p, int& tile, i
 }
 
 static inline dim3 conv16_grid(Conv16Params& p, int ntiles, int nco, int gz = 1) {
-    static const int on = getenv("LP_CONV_XCD") ? atoi(getenv("LP_CONV_XCD")) : 1;
+    const int on = lp_knobs().conv_xcd;
     p.ntiles = ntiles; p.nco = nco;
     p.xcd_map = (on && nco > 1 && ntiles >= 16) ? on : 0;
     if (!p.xcd_map) return dim3(ntiles, nco, gz);

@@ -29,7 +29,6 @@
 #include "conv_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
-#include <stdlib.h>
 #include <type_traits>
 
 __device__ __attribute__((aligned(64))) unsigned int lp_zero_page[16];      // what out-of-image / out-of-channel DMA lanes read
@@ -64,8 +63,7 @@ void conv_dma_kernel(Conv16Params p) {
     constexpr int AIT = ((BM == 128) ? (NWAVE == 8 ? 3 : 5) : 6) * (CC / 32) - (CC == 64 ? 1 : 0);     // max halo DMA instructions per wave (host checks p.hit <= AIT)
     constexpr int NBW = ((NQ + NWD - 1) / NWD) * (SPLIT ? 2 : 1);     // weight DMA instructions one wave issues per stage
     static_assert(B_STAGE % 1024 == 0, "stage must be a whole number of 1 KiB DMA pieces");
-    static_assert(NBUF == 2 || (NBUF == 3 && !PP && NQ % NWD == 0) || (NBUF == 1 && !PP && KS == 1),
-                  "3-deep weight ring: single group, uniform DMA count per wave; NBUF = 1: pointwise layers, ONE weight stage + double-buffered activations");
+    static_assert(NBUF == 2 || (NBUF == 3 && !PP && NQ % NWD == 0), "3-deep weight ring: single group, uniform DMA count per wave");
     static_assert(!PP || ((KS == 3 || KS == 2) && NWAVE == 4), "ping-pong: two 4-wave groups, 3x3 (or the 2x2 phase form)");
     static_assert(!(UPS && KS != 3), "1x1 convs commute with nearest upsampling: run them at low resolution; KS = 2 IS the phase form of an upsampled 3x3 conv");
     static_assert(KS == 1 || KS == 2 || KS == 3, "kernel sizes");
@@ -311,21 +309,6 @@ void conv_dma_kernel(Conv16Params p) {
         // NBUF == 3 (grids of <= 1 workgroup per CU, where nothing else hides the L2/HBM latency of a stage's weights): the DMA of
         // stage s+1 stays in flight across the barrier -- only what stage s needs (everything older, in issue order) is waited for.
         int abuf = 0;
-        if constexpr (NBUF == 1) {
-            // pointwise layers bound by their activation traffic (round 6): the ACTIVATION chunk -- the operand that comes from HBM -- is double
-            // buffered and prefetched one chunk ahead; the weight stage -- L2 resident, a third of the latency -- has ONE buffer and is restaged
-            // after the chunk's MFMAs.  Same LDS as one activation buffer + two weight stages (three workgroups per CU), but what a chunk now
-            // waits for is an L2 hit instead of an HBM round trip.
-            for (int chunk = 0; chunk < nch; ++chunk) {
-                const bool has_next = chunk + 1 < nch;
-                lp_wait_vm0();
-                __syncthreads();
-                if (has_next) issue_halo(cbeg + chunk + 1, H_base + __builtin_amdgcn_readfirstlane((abuf ^ 1) * a_buf));      // (the DMA's LDS base travels in m0: an SGPR)
-                compute(0, H_base + abuf * a_buf, 0, cbeg + chunk);
-                if (has_next) { __syncthreads(); issue_b(cbeg + chunk + 1, 0, 0); }
-                abuf ^= 1;
-            }
-        } else {
         if (NBUF == 3 && S > 1) issue_b(cbeg + 1 / KS, 1 % KS, 1);
         for (int chunk = 0; chunk < nch; ++chunk) {
             const bool has_next = chunk + 1 < nch;
@@ -347,7 +330,6 @@ void conv_dma_kernel(Conv16Params p) {
                 }
             }
             if (p.a_dbuf) abuf ^= 1;
-        }
         }
     }
 
@@ -454,27 +436,17 @@ static int launch_conv16(Conv16Params& p, hipStream_t stream) {
     p.hit = (NH + NWAVE - 1) / NWAVE;
     if (p.hit > AIT) return lp_set_error(LP_ERR_UNSUPPORTED, "conv16: halo exceeds the DMA descriptor budget");
     const size_t a_buf = (size_t)p.hit * NWAVE * 1024 * (SPLIT ? 2 : 1);
-    static const int adbuf_env = getenv("LP_CONV_ADBUF") ? atoi(getenv("LP_CONV_ADBUF")) : -1;      // 0: one A buffer also where two fit (A/B knob)
     p.a_dbuf = (2 * a_buf + 2 * B_BUF <= LDS_MAX) ? 1 : 0;
-    if (adbuf_env == 0 && KS == 1) p.a_dbuf = 0;
     // bf16x3 pointwise layers with short contractions (<= 8 chunks: the layers bound by their traffic): one activation buffer, i.e. a
     // third resident workgroup per CU, beats the double buffer (longer contractions lose 5 - 10 % with it and keep two)
-    if (adbuf_env < 0 && KS == 1 && SPLIT && CC == 32 && p.CinP <= 256) p.a_dbuf = 0;
-    // LP_CONV1X1_B1=1 (round 6 experiment, OFF): those layers with TWO activation buffers and ONE weight stage instead (NBUF = 1 schedule of the kernel):
-    // the HBM round trip of every activation chunk is hidden behind the previous chunk's MFMAs -- and NOTHING moves (119.8 -> 117.4 us at 262 k pixels x
-    // 128 -> 256, 107.2 -> 105.2 us at 256 -> 128; = 2: also the longer contractions, 5 - 20 % slower: profiles/r06_conv1x1_schedules.txt).  The layers'
-    // times fit  bytes / 8.7 TB/s + MFMA work / 0.7 PF/s: what bounds them is the matrix pipe's stage loop (16 fragment reads per 48 MFMAs and a barrier
-    // per 32-channel stage), not the exposed latency of their activation traffic.
-    static const int b1_env = getenv("LP_CONV1X1_B1") ? atoi(getenv("LP_CONV1X1_B1")) : 0;
-    const bool b1 = KS == 1 && CC == 32 && ((b1_env && !p.a_dbuf) || (b1_env >= 2 && SPLIT && BN == 128));          // 2: also the longer bf16x3 contractions
-    if (b1) p.a_dbuf = 1;
+    if (KS == 1 && SPLIT && CC == 32 && p.CinP <= 256) p.a_dbuf = 0;
     const size_t lds_halo = (p.a_dbuf ? 2 : 1) * a_buf;
-    size_t lds = lds_halo + (b1 ? 1 : 2) * B_BUF;
+    size_t lds = lds_halo + 2 * B_BUF;
     size_t epi = (size_t)NWAVE * ((KS == 1) ? 16 : MR * 16) * (NR * 16 + 4) * sizeof(float);      // LDS transpose of the coalesced epilogue (1x1: 16 rows per wave at a time)
     const int tiles = p.tiles_x * p.tiles_y * ((p.N + NBv - 1) / NBv) * (phf ? 4 : 1);          // (forward phase form: every tile position once per phase)
     // ping-pong: two adjacent M tiles per workgroup, when the paired grid still covers the CUs.  LP_CONV_PP = 0 | 1 overrides.
     constexpr bool pp_ok = (KS == 3 || KS == 2) && (NWAVE == 4);
-    static const int pp_env = getenv("LP_CONV_PP") ? atoi(getenv("LP_CONV_PP")) : -1;
+    const int pp_env = lp_knobs().conv_pp;
     const long long pp_wgs = (long long)((tiles + 1) / 2) * ((p.Cout + BN - 1) / BN);
     // (the two groups of a ping-pong workgroup share their weight stages: in the phase form a pair of tiles must not straddle two phases)
     const bool pp = pp_ok && (pp_env >= 0 ? pp_env != 0 : pp_wgs >= 200) && tiles >= 2 && p.a_dbuf && (!phf || ((p.tiles_x * p.tiles_y) & 1) == 0);
@@ -486,8 +458,7 @@ static int launch_conv16(Conv16Params& p, hipStream_t stream) {
     {   // split-K when the output tiling alone cannot fill the 256 CUs (4x4 ... 16x16 layers with K = 9*512): grid.z slices of the
         // contraction write partial tiles into the caller's workspace, splitk_reduce_kernel (launched by lp_conv16_fwd) finishes.
         // 1x1 convs are not split: their whole contraction is 16 stages, less than the cost of a second launch.
-        static const int max_split = getenv("LP_CONV_KSPLIT") ? atoi(getenv("LP_CONV_KSPLIT")) : 8;
-        static const int split_wgs = getenv("LP_CONV_SPLIT_WGS") ? atoi(getenv("LP_CONV_SPLIT_WGS")) : 256;   // split while <= this many workgroups result
+        const int max_split = lp_knobs().conv_ksplit, split_wgs = lp_knobs().conv_split_wgs;      // (lp_conv16_fwd_workspace_bytes bounds the workspace by the same two)
         const int wgs = grid.x * grid.y, nch = (p.CinP / CC) * (phd ? 4 : 1);
         int ks = 1;
         if ((KS == 3 || KS == 2) && (p.Cout & 3) == 0 && p.part)
@@ -513,15 +484,12 @@ static int launch_conv16(Conv16Params& p, hipStream_t stream) {
                         rows * p.Cout * 3 <= p.stats_cap && (!phf || NBv == 1);
         if (ok) p.stats_rows = (p.H * p.W) / WR; else p.stats = nullptr;
     }
-    // (64-channel chunks -- CC = 64, twice the MFMAs between two barriers -- were measured 7-15 % SLOWER on the 64^2..256^2 layers: their
-    //  146 KB of LDS leave one workgroup per CU, while the 72 KB of the 32-channel kernel let two ping-pong workgroups share a CU)
     if constexpr (pp_ok) { if (pp) return launch_v<KS, UPS, WM, WN, MR, NR, PREC, true, 2, CC, GH>(p, lds, grid, stream); }
-    if constexpr (KS == 1 && CC == 32 && !GH) { if (b1) return launch_v<KS, UPS, WM, WN, MR, NR, PREC, false, 1, CC, GH>(p, lds, grid, stream); }
     // 3-deep weight ring when the grid gives each CU at most ~one workgroup (its LDS would exclude a second one anyway) and it fits
     constexpr int NQ = KS * BN * ROWB / 1024;
     constexpr bool ring_ok = (NQ % NWAVE == 0);
-    static const int nbuf_env = getenv("LP_CONV_NBUF") ? atoi(getenv("LP_CONV_NBUF")) : 0;      // 2 | 3 forces
     if constexpr (ring_ok) {
+        const int nbuf_env = lp_knobs().conv_nbuf;      // 2 | 3 forces
         const size_t lds3 = lds_halo + 3 * B_BUF;
         const long long total_wgs = (long long)grid.x * grid.y * grid.z;
         const bool ring = (nbuf_env ? nbuf_env == 3 : total_wgs <= 320) && lds3 <= LDS_MAX;
@@ -549,30 +517,16 @@ static int dispatch_conv16(Conv16Params& p, int ks, int ups, hipStream_t s) {
     const bool big_img = p.H * p.W >= 256;     // a 256-pixel patch fits inside one image
     // 8-wave groups (two waves per SIMD, each 64 x 32 of the 128 x 128 tile) for the small feature maps (<= 16x16): those run
     // split-K with few stages per workgroup, so prologue and epilogue dominate.  LP_CONV_W8 = 0 | 1 forces it off / on.
-    static const int w8_env = getenv("LP_CONV_W8") ? atoi(getenv("LP_CONV_W8")) : -1;
+    const int w8_env = lp_knobs().conv_w8;
     const bool w8 = w8_env >= 0 ? (w8_env != 0) : (p.H * p.W <= 256);
     if (w8 && p.Cout > 64) {
-        // bf16x3 small maps (round 6, LP_CONV_X3_BN64=0 restores the 128 x 128 tile): the 8-wave 128 x 128 tile's hi + lo weight stages (49 KB each) leave no room for the 3-deep
-        // ring, so every stage drains vmcnt(0); 128 x 64 tiles of four waves (24.5 KB stages) keep the ring and double the workgroups per slice
-        static const int x3bn64 = getenv("LP_CONV_X3_BN64") ? atoi(getenv("LP_CONV_X3_BN64")) : 1;      // measured (profiles/r06_x3_small_maps.txt): 4x4 23.2 -> 17.7 us, 8x8 25.4 -> 23.3, 8x8 upsampled 26.0 -> 21.9, 16x16 unchanged; step -0.35 ms
-        if (PREC == LP_PREC_BF16X3 && x3bn64 && ks == 3) {
-            if (!ups) return launch_conv16<3, false, 2, 2, 4, 2, PREC>(p, s);
-            return launch_conv16<3, true, 2, 2, 4, 2, PREC>(p, s);
+        if (ks == 3) {
+            // bf16x3: the 8-wave 128 x 128 tile's hi + lo weight stages (49 KB each) leave no room for the 3-deep ring; 128 x 64 tiles of four
+            // waves (24.5 KB stages) keep it and double the workgroups per slice (profiles/r06_x3_small_maps.txt: -8 .. -24 % on <= 8 x 8 maps)
+            if constexpr (PREC == LP_PREC_BF16X3) return ups ? launch_conv16<3, true, 2, 2, 4, 2, PREC>(p, s) : launch_conv16<3, false, 2, 2, 4, 2, PREC>(p, s);
+            else return ups ? launch_conv16<3, true, 2, 4, 4, 2, PREC>(p, s) : launch_conv16<3, false, 2, 4, 4, 2, PREC>(p, s);
         }
-        if (ks == 3 && !ups) return launch_conv16<3, false, 2, 4, 4, 2, PREC>(p, s);
-        if (ks == 3 && ups) return launch_conv16<3, true, 2, 4, 4, 2, PREC>(p, s);
         if (ks == 1 && !ups) return launch_conv16<1, false, 2, 4, 4, 2, PREC>(p, s);
-    }
-    if (PREC == LP_PREC_BF16X3 && ks == 3 && p.Cout > 64) {
-        // bf16x3 layers whose paired (ping-pong) grid would not cover the chip (e.g. 32 x 32 x 512 at N = 8: 256 workgroups of 128 x 128) fall to the
-        // single-group kernel, whose doubled weight stages do not fit a 3-deep ring either: the same 128 x 64 four-wave tile as the small maps
-        // (LP_CONV_X3_BN64=2 enables it; measured in profiles/r06_x3_small_maps.txt)
-        static const int x3mid = getenv("LP_CONV_X3_BN64") ? atoi(getenv("LP_CONV_X3_BN64")) : 1;
-        const long long tiles128 = ((long long)p.N * p.H * p.W + 127) / 128;
-        if (x3mid >= 2 && ((tiles128 + 1) / 2) * ((p.Cout + 127) / 128) < 200) {
-            if (!ups) return launch_conv16<3, false, 2, 2, 4, 2, PREC>(p, s);
-            return launch_conv16<3, true, 2, 2, 4, 2, PREC>(p, s);
-        }
     }
     if (ks == 3 && !ups) {
         if (p.Cout <= 16 && big_img) return launch_conv16<3, false, 4, 1, 4, 1, PREC>(p, s);
@@ -585,28 +539,15 @@ static int dispatch_conv16(Conv16Params& p, int ks, int ups, hipStream_t s) {
     }
     if (ks == 1 && !ups) {
         // 1x1: one tap per chunk, so a 32-channel stage is 16 MFMAs per wave between two barriers.  With >= 512 input channels and single-plane
-        // operands the stage is a 64-channel chunk (32 MFMAs, half the barriers): +3..12% on the embedder's K >= 512 layers, nothing below
-        // (those are bound by the fp32 output store), and SLOWER with bf16x3's doubled planes (LDS per workgroup doubles again, occupancy
-        // drops) -- profiles/r03_conv1x1_cc64.txt.  LP_CONV_CC1 = 32 | 64 forces.
-        static const int cc_env = getenv("LP_CONV_CC1") ? atoi(getenv("LP_CONV_CC1")) : 0;
-        const bool cc64 = (cc_env ? cc_env == 64 : (p.Cin >= 512 && PREC != LP_PREC_BF16X3)) && (p.CinP % 64 == 0);
-        // LP_CONV1X1_TILE=256: 256 x 128 output tiles (8 waves, 64 x 64 each) for the big pointwise layers -- 25 % fewer operand bytes staged
-        // L2 -> LDS per flop than the 128 x 128 tile.  Measured NULL (profiles/r03_conv1x1_tile256.txt: every layer within +-5 %, the step
-        // 39.4 vs 39.3 ms), so the K >= 512 layers' ~470-600 TF/s is not an L2-bandwidth limit but the one-stage-ahead DMA + barrier per stage
-        // of this loop; the default stays 128.
-        static const int tile_env = getenv("LP_CONV1X1_TILE") ? atoi(getenv("LP_CONV1X1_TILE")) : 0;
-        const long long pix = (long long)p.N * p.H * p.W;
-        const bool tall = (tile_env ? tile_env == 256 : false) && p.Cout >= 128 && p.H * p.W >= 256 &&
-                          (pix / 256) * ((p.Cout + 127) / 128) >= 512;
-        if (cc64) {
-            if (p.Cout <= 64 && big_img) return launch_conv16<1, false, 4, 1, 4, 4, PREC, 64>(p, s);
-            if (tall) return launch_conv16<1, false, 4, 2, 4, 4, PREC, 64>(p, s);
-            return launch_conv16<1, false, 2, 2, 4, 4, PREC, 64>(p, s);
+        // operands the stage is a 64-channel chunk (32 MFMAs, half the barriers): +3..12% on the embedder's K >= 512 layers, nothing below (bound
+        // by the fp32 output store), SLOWER with bf16x3's doubled planes (twice the LDS, occupancy drops) -- profiles/r03_conv1x1_cc64.txt
+        if constexpr (PREC != LP_PREC_BF16X3) {
+            if (p.Cin >= 512 && p.CinP % 64 == 0) {
+                if (p.Cout <= 64 && big_img) return launch_conv16<1, false, 4, 1, 4, 4, PREC, 64>(p, s);
+                return launch_conv16<1, false, 2, 2, 4, 4, PREC, 64>(p, s);
+            }
         }
         if (p.Cout <= 64 && big_img) return launch_conv16<1, false, 4, 1, 4, 4, PREC>(p, s);
-        if (tall) return launch_conv16<1, false, 4, 2, 4, 4, PREC>(p, s);
-        // (round 6, measured and removed: 128 x 64 tiles for the bf16x3 layers with short contractions -- 41.6 -> 54.8 us, 119.8 -> 154.7 us,
-        //  profiles/r06_conv1x1_schedules.txt)
         return launch_conv16<1, false, 2, 2, 4, 4, PREC>(p, s);
     }
     return lp_set_error(LP_ERR_UNSUPPORTED, "unsupported conv configuration");
@@ -617,9 +558,7 @@ extern "C" long long lp_conv16_fwd_workspace_bytes(int N, int H, int W, int Cout
     if (ksize != 3 || (Cout & 3)) return 0;
     const long long P = (long long)N * H * W;
     const long long wgs_lb = ((P + 255) / 256) * ((Cout + 127) / 128);
-    static const int max_split = getenv("LP_CONV_KSPLIT") ? atoi(getenv("LP_CONV_KSPLIT")) : 8;         // (the knobs of launch_conv16)
-    static const int split_wgs = getenv("LP_CONV_SPLIT_WGS") ? atoi(getenv("LP_CONV_SPLIT_WGS")) : 256;
-    long long ks = split_wgs / wgs_lb; if (ks > max_split) ks = max_split;
+    long long ks = lp_knobs().conv_split_wgs / wgs_lb; if (ks > lp_knobs().conv_ksplit) ks = lp_knobs().conv_ksplit;      // (as launch_conv16 splits)
     if (ks < 2) return 0;
     return ks * P * Cout * (long long)sizeof(float);
 }
@@ -736,9 +675,8 @@ extern "C" int lp_gconv16_fwd_planes(const uint16_t* a_hi, const uint16_t* a_lo,
         return rc > 0 ? LP_OK : rc;
     }
     // group_size (0: unknown) in 1 .. 32: the two 32-channel halves of a 64-channel block do not interact -- the kernel variant that skips
-    // the zero half of every stage (LP_GCONV_HALF=0: the full block-diagonal product, the A/B baseline)
-    static const bool half_env = !(getenv("LP_GCONV_HALF") && atoi(getenv("LP_GCONV_HALF")) == 0);
-    const bool gh = half_env && group_size >= 1 && group_size <= 32 && (32 % group_size) == 0;
+    // the zero half of every stage (other group sizes: the full block-diagonal product)
+    const bool gh = group_size >= 1 && group_size <= 32 && (32 % group_size) == 0;
     if (prec == LP_PREC_BF16) rc = gh ? launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_BF16, 32, true>(p, s) : launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_BF16>(p, s);
     else if (prec == LP_PREC_BF16X3) rc = gh ? launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_BF16X3, 32, true>(p, s) : launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_BF16X3>(p, s);
     else if (prec == LP_PREC_F16) rc = gh ? launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_F16, 32, true>(p, s) : launch_conv16<3, false, 4, 1, 4, 4, LP_PREC_F16>(p, s);

@@ -23,7 +23,6 @@
 #include "conv_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
-#include <stdlib.h>
 
 static __device__ __attribute__((aligned(64))) unsigned int lp_zero_page_pipe[16];      // what out-of-image DMA lanes read
 
@@ -422,18 +421,17 @@ static int pipe1x1_dispatch(Conv16Params& p, int bn, hipStream_t s) {
 
 // -> 1: launched; 0: not covered; < 0: error
 int lp_conv1x1_pipe_launch(Conv16Params& p, int prec, hipStream_t s) {
-    // OFF by default (round 4, profiles/r04_conv1x1_pipe.txt): the pointwise layers turned out to be bound by HBM traffic and by how many
-    // workgroups a CU holds, not by the chunk-by-chunk DMA round trips -- the ring costs LDS (64 / 96 KB per workgroup against 32 / 64 KB),
-    // i.e. a resident workgroup per CU, and the kernel measured 5 - 25 % SLOWER than conv_dma_kernel<1> on the layers that carry the bytes
-    // (fp16: 79 -> 87 us at 262 k pixels x 128 -> 256; bf16x3: 137 -> 167 us), equal on the long contractions.  1: on; 2: every shape (tests).
-    static const int on = getenv("LP_CONV1X1_PIPE") ? atoi(getenv("LP_CONV1X1_PIPE")) : 0;
+    // OFF by default (round 4, profiles/r04_conv1x1_pipe.txt): the ring costs LDS (64 / 96 KB per workgroup against 32 / 64 KB), i.e. a resident
+    // workgroup per CU, and the kernel measured 5 - 25 % SLOWER than conv_dma_kernel<1> on the layers that carry the bytes, equal on the long
+    // contractions.  1: on; 2: every shape (tests).
+    const int on = lp_knobs().conv1x1_pipe;
+    constexpr int MAXK = 256;
     if (!on || p.grouped || p.CinP % 32 || p.H < 2 || p.W < 2) return 0;
     const long long pix = (long long)p.N * p.H * p.W;
     const int bn = p.Cout <= 64 ? 64 : 128;
     const long long wgs = ((pix + (bn == 64 ? 255 : 127)) / (bn == 64 ? 256 : 128)) * ((p.Cout + bn - 1) / bn);
-    static const int maxk = getenv("LP_CONV1X1_PIPE_MAXK") ? atoi(getenv("LP_CONV1X1_PIPE_MAXK")) : 256;
-    // small layers: the 8-wave paths of conv_dma_kernel; long contractions (> maxk input channels): its 64-channel stages
-    if (on != 2 && (wgs < 256 || p.CinP > maxk)) return 0;
+    // small layers: the 8-wave paths of conv_dma_kernel; long contractions (> MAXK input channels): its 64-channel stages
+    if (on != 2 && (wgs < 256 || p.CinP > MAXK)) return 0;
     if (prec == LP_PREC_BF16) return pipe1x1_dispatch<LP_PREC_BF16>(p, bn, s);
     if (prec == LP_PREC_BF16X3) return pipe1x1_dispatch<LP_PREC_BF16X3>(p, bn, s);
     if (prec == LP_PREC_F16) return pipe1x1_dispatch<LP_PREC_F16>(p, bn, s);
@@ -494,20 +492,17 @@ static int pipe_dispatch(Conv16Params& p, int ups, int mr, int bn, hipStream_t s
 
 // -> 1: launched; 0: this layer is not covered (the caller runs conv_dma_kernel); < 0: error.  p: as filled by lp_conv16_fwd_stats.
 int lp_conv_pipe_launch(Conv16Params& p, int ups, int prec, hipStream_t s) {
-    static const int on = getenv("LP_CONV_PIPE") ? atoi(getenv("LP_CONV_PIPE")) : 1;
-    static const int mr_env = getenv("LP_CONV_PIPE_MR") ? atoi(getenv("LP_CONV_PIPE_MR")) : 0;      // 4 | 8 forces the rows per wave (test knob)
-    static const int n64 = getenv("LP_CONV_PIPE_N64") ? atoi(getenv("LP_CONV_PIPE_N64")) : 1;       // 0: <= 64-channel outputs stay on conv_dma_kernel
-    static const int x3 = getenv("LP_CONV_PIPE_X3") ? atoi(getenv("LP_CONV_PIPE_X3")) : 0;
-    if (!on || p.grouped) return 0;
+    const int mr_env = lp_knobs().conv_pipe_mr;      // 4 | 8 forces the rows per wave (test knob)
+    if (!lp_knobs().conv_pipe || p.grouped) return 0;
     // bf16x3 (hi + lo planes: 144 KB of LDS, one workgroup per CU, compiler-scheduled MFMAs): measured SLOWER than conv_dma_kernel on the
-    // 64^2 .. 128^2 layers (115 vs 86 .. 93 us, profiles/r04_conv_pipe_micro.txt) -- the strict mode stays on conv_dma_kernel unless forced
-    // (LP_CONV_PIPE_X3=1, or the test knob LP_CONV_PIPE_MR)
-    if (prec == LP_PREC_BF16X3 && !x3 && !mr_env) return 0;
+    // 64^2 .. 128^2 layers (115 vs 86 .. 93 us, profiles/r04_conv_pipe_micro.txt) -- the strict mode stays on conv_dma_kernel unless the
+    // test knob forces it
+    if (prec == LP_PREC_BF16X3 && !mr_env) return 0;
     if ((p.C8 & 31) || p.CinP % 32 || p.W < 16 || p.H < 16) return 0;
     int mr = 0, bn = 128;
     const long long px_tiles = (long long)((p.W + 15) / 16) * p.N;
     if (p.Cout <= 64) {
-        if (!n64 || p.Cout < 32) return 0;                 // (the 4- / 3-channel head and RGB layers have their own kernels)
+        if (p.Cout < 32) return 0;               // (the 4- / 3-channel head and RGB layers have their own kernels)
         const long long t = px_tiles * ((p.H + 15) / 16);
         if (t < 400 && !mr_env) return 0;
         bn = 64; mr = 4;

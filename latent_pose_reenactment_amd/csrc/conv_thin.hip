@@ -247,8 +247,7 @@ __global__ __launch_bounds__(256) void conv_rgb_mfma_kernel(RgbMfmaParams p) {
 static size_t rgb_mfma_lds(int W) { return ((rows_lds_bytes(4, 1, W, 8) + 15) & ~(size_t)15) + (size_t)4 * 16 * 68 * sizeof(float); }
 
 static bool rgb_mfma_ok(int Cin, int Cout, int ksize, int W, int prec) {
-    static const int env = getenv("LP_THIN_MFMA") ? atoi(getenv("LP_THIN_MFMA")) : 1;       // LP_THIN_MFMA=0: fp32 VALU kernel always
-    return env && Cin == 3 && ksize == 3 && (Cout % 64) == 0 && (W % 16) == 0 && prec != LP_PREC_BF16X3 &&
+    return lp_knobs().thin_mfma && Cin == 3 && ksize == 3 && (Cout % 64) == 0 && (W % 16) == 0 && prec != LP_PREC_BF16X3 &&
            rgb_mfma_lds(W) <= 64 * 1024;
 }
 

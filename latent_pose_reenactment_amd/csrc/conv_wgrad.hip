@@ -12,7 +12,6 @@
 #include "lp_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
-#include <stdlib.h>
 
 struct WgradParams {
     const uint16_t* a_hi; const uint16_t* a_lo; const uint16_t* d_hi; const uint16_t* d_lo; float* part;
@@ -504,7 +503,7 @@ struct W1Params {
 static __device__ __attribute__((aligned(64))) unsigned int w1_zero_page[16];      // what out-of-range DMA lanes read
 
 // KP = pixels per stage: 64; 32 in the bf16x3 mode, whose doubled planes would otherwise need 128 KB of LDS -- ONE workgroup per CU for a kernel
-// bound by its operand stream (round 4: two 64 KB workgroups per CU, profiles/r04_wgrad1x1_x3.txt; LP_W1_KP = 64 restores the old stage)
+// bound by its operand stream (round 4: two 64 KB workgroups per CU, profiles/r04_wgrad1x1_x3.txt).  Each mode is built with its own KP only.
 template <int PREC, int KP>
 __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(W1Params p) {
     constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
@@ -878,7 +877,7 @@ __global__ __launch_bounds__(256, (PREC == LP_PREC_BF16X3 && DIAGB == 0) ? 1 : 2
 template <bool UPS, int PREC, int DIAGB = 0>
 static int launch_wgrad3_pipe(WgradParams& p, float* dw, float* dbias, const float* out_scale, const float* sn_w, float* sn_dot, hipStream_t stream) {
     constexpr bool SPLIT = (PREC == LP_PREC_BF16X3);
-    static const int target_env = getenv("LP_WGRAD3_WGS") ? atoi(getenv("LP_WGRAD3_WGS")) : 0;
+    constexpr int TARGET_WGS = SPLIT ? 512 : 1024;         // ~2 resident sets of two (bf16x3: one) workgroups per CU
     W3Params q;
     q.a_hi = p.a_hi; q.a_lo = p.a_lo; q.d_hi = p.d_hi; q.d_lo = p.d_lo; q.part = p.part; q.bpart = p.bpart;
     q.N = p.N; q.H = p.H; q.W = p.W; q.Hin = p.Hin; q.Win = p.Win; q.C8 = p.C8; q.Co8 = p.Co8; q.CoP = p.CoP; q.CiP = p.CiP;
@@ -887,8 +886,7 @@ static int launch_wgrad3_pipe(WgradParams& p, float* dw, float* dbias, const flo
     q.num_tiles = q.tiles_x * q.tiles_y * p.N;
     q.tiles_co = p.CoP / 64; q.tiles_ci = p.diag ? 1 : p.CiP / 64;
     const int ntile = q.tiles_co * q.tiles_ci;
-    const int target = target_env > 0 ? target_env : (SPLIT ? 512 : 1024);    // ~2 resident sets of two (bf16x3: one) workgroups per CU
-    int splits = target / ntile; if (splits < 1) splits = 1;
+    int splits = TARGET_WGS / ntile; if (splits < 1) splits = 1;
     if (splits > p.splits) splits = p.splits;
     if (splits > q.num_tiles) splits = q.num_tiles;
     if (splits >= 8) splits = splits / 8 * 8;
@@ -914,17 +912,16 @@ static int launch_wgrad3_pipe(WgradParams& p, float* dw, float* dbias, const flo
     return launch_wreduce(p, 9, dw, dbias, out_scale, sn_w, sn_dot, stream);
 }
 
-// LP_WGRAD3_PIPE = 0: conv_wgrad_kernel everywhere | 1 (default): the DMA-staged kernel for layers with >= LP_WGRAD3_MIN_TILES (32) pixel
-// tiles and W >= 16 | 2: for every 3x3 layer of a one-plane mode (tests)
+// the DMA-staged kernel takes the layers with >= MIN_TILES pixel tiles and W >= 16 (lp_knobs.h: LP_WGRAD3_PIPE, LP_WGRAD3_X3)
 template <int PREC>
 static bool wgrad3_pipe_wanted(const WgradParams& p, bool diag_form = false) {
-    static const int x3 = getenv("LP_WGRAD3_X3") ? atoi(getenv("LP_WGRAD3_X3")) : 1;          // dense bf16x3 layers on this kernel (round 6: -4 .. -9 % per layer, profiles/r06_wgrad3_x3.txt; 0: conv_wgrad_kernel)
-    if (PREC == LP_PREC_BF16X3 && !diag_form && !x3) return false;
-    static const int mode = getenv("LP_WGRAD3_PIPE") ? atoi(getenv("LP_WGRAD3_PIPE")) : 1;
-    static const int min_tiles = getenv("LP_WGRAD3_MIN_TILES") ? atoi(getenv("LP_WGRAD3_MIN_TILES")) : 32;
+    constexpr int MIN_TILES = 32;
+    // (dense bf16x3 layers on this kernel: round 6, -4 .. -9 % per layer, profiles/r06_wgrad3_x3.txt)
+    if (PREC == LP_PREC_BF16X3 && !diag_form && !lp_knobs().wgrad3_x3) return false;
+    const int mode = lp_knobs().wgrad3_pipe;
     if (mode == 0) return false;
     if (mode == 2) return true;
-    return p.W >= 16 && p.H >= 8 && ((p.W + 15) / 16) * ((p.H + 7) / 8) * p.N >= min_tiles;
+    return p.W >= 16 && p.H >= 8 && ((p.W + 15) / 16) * ((p.H + 7) / 8) * p.N >= MIN_TILES;
 }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -940,22 +937,15 @@ template <int PREC>
 static int dispatch_wgrad(WgradParams& p, float* dw, float* dbias, const float* out_scale, const float* sn_w, float* sn_dot, int ksize,
                           int upsample, hipStream_t s) {
     // 128 output channels per workgroup (8 waves) where the layer is wide enough; LP_WGRAD_COB = 64 | 128 overrides
-    static const int cob_env = getenv("LP_WGRAD_COB") ? atoi(getenv("LP_WGRAD_COB")) : 0;
+    const int cob_env = lp_knobs().wgrad_cob;
     const bool cob128 = cob_env ? (cob_env == 128) : true;      // measured: -9 % (bf16x3), -6 % (bf16) on the 64..512-channel layers
     if (ksize == 3 && wgrad3_pipe_wanted<PREC>(p))
         return upsample ? launch_wgrad3_pipe<true, PREC>(p, dw, dbias, out_scale, sn_w, sn_dot, s) : launch_wgrad3_pipe<false, PREC>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
     if (cob128 && p.Cout >= 128 && ksize == 3)
         return upsample ? launch_wgrad<3, true, PREC, 128>(p, dw, dbias, out_scale, sn_w, sn_dot, s) : launch_wgrad<3, false, PREC, 128>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
-    static const bool w1_old = getenv("LP_WGRAD1X1_OLD") != nullptr;                              // A/B knob: the generic kernel for 1x1 layers
-    static const int w1_kp = getenv("LP_W1_KP") ? atoi(getenv("LP_W1_KP")) : 0;                   // bf16x3 stage: 32 (default) | 64 pixels
-    if (ksize == 1 && !upsample && !p.bpart && !w1_old) {
-        const int kp = w1_kp ? w1_kp : (PREC == LP_PREC_BF16X3 ? 32 : 64);
-        if (kp == 32) return launch_wgrad1x1<PREC, 32>(p, dw, out_scale, sn_w, sn_dot, s);
-        return launch_wgrad1x1<PREC, 64>(p, dw, out_scale, sn_w, sn_dot, s);
-    }
-    static const int cob1_env = getenv("LP_WGRAD_COB1") ? atoi(getenv("LP_WGRAD_COB1")) : 0;        // 1x1 layers: 64 | 128 forces
-    if ((cob1_env ? cob1_env == 128 : true) && p.Cout >= 128 && ksize == 1 && !upsample)
-        return launch_wgrad<1, false, PREC, 128>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
+    if (ksize == 1 && !upsample && !p.bpart)      // (hipops.default_splits picks the split count of this branch)
+        return launch_wgrad1x1<PREC, (PREC == LP_PREC_BF16X3 ? 32 : 64)>(p, dw, out_scale, sn_w, sn_dot, s);
+    if (p.Cout >= 128 && ksize == 1 && !upsample) return launch_wgrad<1, false, PREC, 128>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
     if (ksize == 3 && !upsample) return launch_wgrad<3, false, PREC>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
     if (ksize == 3 && upsample) return launch_wgrad<3, true, PREC>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
     if (ksize == 1 && !upsample) return launch_wgrad<1, false, PREC>(p, dw, dbias, out_scale, sn_w, sn_dot, s);
@@ -1034,9 +1024,8 @@ extern "C" int lp_gconv16_wgrad(const uint16_t* a_hi, const uint16_t* a_lo, cons
     p.splits = splits; p.db_acc = 0; p.diag = 1; p.bpart = nullptr;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    // groups of <= 16 / 32 channels: the DMA-staged kernel on the non-zero diagonal tiles only (LP_GWGRAD_DIAG=0: the dense 64 x 64 block)
-    static const bool diag_env = !(getenv("LP_GWGRAD_DIAG") && atoi(getenv("LP_GWGRAD_DIAG")) == 0);
-    const int db = !diag_env ? 0 : (group_size <= 16 && 16 % group_size == 0) ? 16 : (group_size == 32 ? 32 : 0);
+    // groups of <= 16 / 32 channels: the DMA-staged kernel on the non-zero diagonal tiles only (other group sizes: the dense 64 x 64 block)
+    const int db = (group_size <= 16 && 16 % group_size == 0) ? 16 : (group_size == 32 ? 32 : 0);
 #define LP_GW3(PR) (db == 16 ? launch_wgrad3_pipe<false, PR, 16>(p, dw, nullptr, out_scale, nullptr, nullptr, s) \
                              : launch_wgrad3_pipe<false, PR, 32>(p, dw, nullptr, out_scale, nullptr, nullptr, s))
     if (db && prec == LP_PREC_BF16 && wgrad3_pipe_wanted<LP_PREC_BF16>(p, true)) rc = LP_GW3(LP_PREC_BF16);

@@ -34,7 +34,6 @@
 #include "conv_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
-#include <stdlib.h>
 
 // (the epilogue's float4 arithmetic: keep hipcc from the packed fp32 forms that are wrong beside the LDS-DMA kernels, tests/test_isa_lint.py)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -270,8 +269,7 @@ __global__ __launch_bounds__(256, PREC == LP_PREC_BF16X3 ? 2 : 4) void gconv_row
 // -> 1: launched; 0: this layer stays on conv_dma_kernel; < 0: error.  p: the parameter block lp_gconv16_fwd_planes filled (p.stats /
 // p.stats_rows are updated as launch_conv16 does: statistics the geometry does not cover are dropped and reported as 0 rows).
 int lp_gconv_rows_launch(Conv16Params& c, int group_size, int prec, hipStream_t s) {
-    static const int mode = getenv("LP_GCONV_ROWS") ? atoi(getenv("LP_GCONV_ROWS")) : 1;      // 0: conv_dma_kernel; 2: every shape this kernel can express
-    static const int wgs_cap = getenv("LP_GCONV_ROWS_WGS") ? atoi(getenv("LP_GCONV_ROWS_WGS")) : 0;      // cap of the workgroups per channel block
+    const int mode = lp_knobs().gconv_rows, wgs_cap = lp_knobs().gconv_rows_wgs;
     if (mode == 0 || !(group_size == 4 || group_size == 8 || group_size == 16)) return 0;
     if (prec != LP_PREC_BF16 && prec != LP_PREC_BF16X3 && prec != LP_PREC_F16) return 0;
     const bool exact = (c.W % gr::TW == 0) && (c.H % gr::TH == 0);      // whole 4 x 16 tiles: nothing multiplied for nothing, one tile = one statistics row block

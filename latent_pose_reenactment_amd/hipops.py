@@ -521,7 +521,7 @@ def default_splits(n, h, w, cin, cout, ksize=3, prec=None, bias=False):
     1x1 without a bias gradient (wgrad1x1_kernel: 128 x 128 weight tiles, 64-pixel stages): one resident set of workgroups -- 2 per CU
     (64 KB of LDS each; 1 per CU for bf16x3's doubled planes) -- each walking >= 8 stages, a multiple of 8 so that the tiles of one
     pixel range share an XCD.  1x1 with a bias gradient (conv_wgrad_kernel): ~4 workgroups per CU, >= 4 128-pixel tiles each."""
-    if ksize == 1 and not bias and os.environ.get('LP_WGRAD1X1_OLD') is None:
+    if ksize == 1 and not bias:
         stages = (n * h * w + 63) // 64
         blocks = (_round_up(cout, 64) + 127) // 128 * ((_round_up(cin, 64) + 127) // 128)
         s = max(1, min(512 // blocks, stages // 8))          # (bf16x3 too since round 4: 32-pixel stages, two workgroups per CU)

@@ -1,6 +1,6 @@
 """Every tile / schedule variant of the HIP kernels must pass the same per-op parity tests, not only the variant the default
-heuristics pick for the (small) test shapes.  The variant knobs are read once per process (static env lookups in
-csrc/conv_dma.hip, conv_wgrad.hip, conv_thin.hip; LP_THIN in hipops.py), so each setting runs tests/test_hip_ops.py in a fresh interpreter."""
+heuristics pick for the (small) test shapes.  The variant knobs are read once per process (the knob table
+csrc/lp_knobs.h, filled on first use; LP_THIN in hipops.py), so each setting runs tests/test_hip_ops.py in a fresh interpreter."""
 import os
 import subprocess
 import sys
