@@ -634,6 +634,27 @@ int lp_jpeg_decode_pixels(const short* coefs, long long coef_blocks, const long 
                           const unsigned char* qtables, const int* idct_host, unsigned char* planes, long long plane_bytes, unsigned char* out,
                           long long out_bytes, void* stream);
 
+/* (additive, ABI 12) Baseline PNG encoder of the lossless outputs (csrc/png.hip holds the definition: 8 bits, grey or RGB, per-row filter choice,
+ * deflate in independent segments of 16384 bytes with run-length matches at distance 1 and one Huffman code per segment, one IDAT).
+ * L = H x (1 + W x C), the length of a frame's filtered stream.
+ * lp_png_filter: frames = DEVICE uint8, logical [T][H][W][C], C = 1 or 3, read through strides = HOST array of 4 element strides (frame, row,
+ * column, channel), read at call time; filtered = DEVICE uint8 [T][L], written.  ONE launch, no atomics, no workspace.
+ * lp_png_deflate_size: filtered = ANY DEVICE uint8 [T][L]; scratch = DEVICE, 16-byte aligned, at least lp_png_deflate_scratch_bytes(T, L) bytes,
+ * contents irrelevant on entry; offsets = DEVICE int64 [T + 1], written: file t will occupy bytes offsets[t] .. offsets[t + 1], offsets[T] is the
+ * size of the output.  Two launches (integer atomics in LDS only: the bytes do not depend on the order of arrival).
+ * lp_png_write: the same scratch, geometry and offsets; head = HOST uint8 [45]: the PNG signature and IHDR chunk (33 bytes) and the IEND chunk (12),
+ * read at call time and passed to the kernel by value; out = DEVICE uint8 [out_bytes] with out_bytes = offsets[T]: writes every file.  ONE launch;
+ * every store is checked against out_bytes.  No call allocates or synchronises: the caller reads offsets[T] between the last two.
+ * LP_ERR_ARG: null pointer, T, H, W or L < 1, C outside {1, 3}, a misaligned or short scratch, out_bytes < 1; LP_ERR_UNSUPPORTED: a grid beyond
+ * one launch, a row above 4194304 bytes, filtered streams, a scratch or an output beyond 2^31 - 1 bytes (lp_png_deflate_scratch_bytes returns the
+ * negative code) -- all checked before any device work. */
+int lp_png_filter(const unsigned char* frames, const long long* strides, int T, int H, int W, int C, unsigned char* filtered, void* stream);
+long long lp_png_deflate_scratch_bytes(int T, long long L);
+int lp_png_deflate_size(const unsigned char* filtered, int T, long long L, void* scratch, long long scratch_bytes, long long* offsets,
+                        void* stream);
+int lp_png_write(const void* scratch, long long scratch_bytes, int T, long long L, const unsigned char* head, const long long* offsets,
+                 unsigned char* out, long long out_bytes, void* stream);
+
 /* ---- fused multi-tensor optimizers + EMA(runners/holycow.py:34-41,99-109; utils/radam.py:29-95; torch.optim.Adam) ----
  * table: DEVICE array of {float* p; const float* g; float* m; float* v; long long n;} (lp_mt_desc_bytes() each), one per
  * parameter tensor; step: DEVICE int64 counter, incremented by the call (graph-replay safe).  kind 0 = RAdam, 1 = Adam.

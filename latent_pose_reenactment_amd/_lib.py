@@ -122,6 +122,10 @@ SIGNATURES = {
     'lp_jpeg_code_table': (_i, [_vp]),
     'lp_jpeg_decode_entropy': (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _vp, _vp]),
     'lp_jpeg_decode_pixels': (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp, _vp, _ll, _vp, _ll, _vp]),
+    'lp_png_filter': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'lp_png_deflate_scratch_bytes': (_ll, [_i, _ll]),
+    'lp_png_deflate_size': (_i, [_vp, _i, _ll, _vp, _ll, _vp, _vp]),
+    'lp_png_write': (_i, [_vp, _ll, _i, _ll, _vp, _vp, _vp, _ll, _vp]),
     'lp_pool_grad_pack':(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'lp_adain_relu_bwd_planes': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'lp_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -1677,6 +1677,271 @@ def jpeg_encode(frames: Tensor, quality: int = 90):
     return jpeg_entropy(jpeg_transform(frames, quality), mjpeg.jpeg_header(h, w, quality))
 
 
+# ---- baseline PNG of the lossless outputs (csrc/png.hip holds the definition) ------------------------------------------------------------------------
+PNG_SEG = 16384                     # bytes of the filtered stream per deflate segment
+PNG_HEADER_BITS = 1222              # the dynamic block header of the definition: 17 + 19 x 3 + 287 x 4
+_PNG_LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_PNG_LEN_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+
+
+def _png_frames(frames, who):
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f'{who}: frames must be a tensor, got {type(frames).__name__}')
+    if frames.dtype != torch.uint8:
+        raise ValueError(f'{who}: frames must be uint8, got {frames.dtype}')
+    if frames.dim() != 4:
+        raise ValueError(f'{who}: frames must be 4-D [T, H, W, C], got shape {tuple(frames.shape)}')
+    t, h, w, c = frames.shape
+    if c not in (1, 3):
+        raise ValueError(f'{who}: frames must be grey or RGB [T, H, W, 1 or 3], got C = {c}')
+    if t < 1 or h < 1 or w < 1:
+        raise ValueError(f'{who}: empty input {tuple(frames.shape)}: T, H and W must be >= 1')
+    return t, h, w, c
+
+
+def _png_stream(filtered, who):
+    if not (isinstance(filtered, torch.Tensor) and filtered.dtype == torch.uint8 and filtered.dim() == 2):
+        raise ValueError(f'{who}: the filtered streams must be a uint8 tensor [T, L], got '
+                         f'{(filtered.dtype, tuple(filtered.shape)) if isinstance(filtered, torch.Tensor) else type(filtered).__name__}')
+    t, n = filtered.shape
+    if t < 1 or n < 1:
+        raise ValueError(f'{who}: empty stream table {tuple(filtered.shape)}: T and L must be >= 1')
+    return t, n
+
+
+def _png_chunk(kind: bytes, data: bytes) -> bytes:
+    import struct
+    import zlib
+    return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data))
+
+
+def _png_head(h: int, w: int, c: int) -> bytes:
+    """the 45 bytes of a file that do not depend on the pixels: signature + IHDR (33), then IEND (12); their CRCs are computed here, on the host"""
+    import struct
+    return b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2 if c == 3 else 0, 0, 0, 0)) + _png_chunk(b'IEND', b'')
+
+
+def _png_stream_head(n: int) -> bytes:
+    """the head ``png_deflate`` gives a stream that comes without a shape: one grey row whose filtered bytes are the stream"""
+    return _png_head(1, max(n - 1, 1), 1)
+
+
+def png_filter_host(frames: Tensor) -> Tensor:
+    """the filtered streams of csrc/png.hip in numpy: uint8 [T, H (1 + W C)], every row its filter type and its filtered bytes"""
+    import numpy as np
+    t, h, w, c = _png_frames(frames, 'png_filter_host')
+    x = frames.detach().cpu().numpy().astype(np.int32)
+    a, b, d = np.zeros_like(x), np.zeros_like(x), np.zeros_like(x)
+    a[:, :, 1:] = x[:, :, :-1]
+    b[:, 1:] = x[:, :-1]
+    d[:, 1:, 1:] = x[:, :-1, :-1]
+    p = a + b - d
+    pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - d)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, d))
+    cands = (np.stack((x, x - a, x - b, x - ((a + b) >> 1), x - paeth)) & 255).reshape(5, t, h, w * c)
+    best = np.argmin(np.where(cands < 128, cands, 256 - cands).sum(-1), axis=0)          # the first minimum: ties to the lowest type
+    rows = np.take_along_axis(cands, best[None, :, :, None], axis=0)[0]
+    out = np.concatenate((best[:, :, None], rows), axis=-1).astype(np.uint8).reshape(t, h * (1 + w * c))
+    return torch.from_numpy(out)
+
+
+def png_code_lengths(hist):
+    """steps 1 .. 4 of the code construction of csrc/png.hip: symbol counts -> code lengths <= 15 (a list as long as ``hist``)"""
+    leaves = sorted((int(n), s) for s, n in enumerate(hist) if n > 0)
+    m = len(leaves)
+    lengths = [0] * len(hist)
+    if m < 2:
+        raise ValueError('png_code_lengths: at least two symbols must occur (a segment holds a byte and the end-of-block symbol)')
+    weight = [n for n, _ in leaves]
+    parent = [0] * (2 * m - 1)
+    li = ii = 0
+    for ni in range(m - 1):
+        w = 0
+        for _ in range(2):
+            if li < m and (ii >= ni or weight[li] < weight[m + ii]):
+                w += weight[li]
+                parent[li] = m + ni
+                li += 1
+            else:
+                w += weight[m + ii]
+                parent[m + ii] = m + ni
+                ii += 1
+        weight.append(w)
+    depth = [0] * (2 * m - 1)
+    for node in range(2 * m - 3, -1, -1):
+        depth[node] = depth[parent[node]] + 1
+    cnt = [0] * (max(depth) + 2)
+    for d in depth[:m]:
+        cnt[d] += 1
+    for deep in range(len(cnt) - 1, 15, -1):
+        while cnt[deep] > 0:
+            b = max(k for k in range(1, 15) if cnt[k] > 0)
+            cnt[b] -= 1
+            cnt[b + 1] += 2
+            cnt[deep] -= 2
+            cnt[deep - 1] += 1
+    i = 0
+    for length in range(min(15, len(cnt) - 1), 0, -1):
+        for _ in range(cnt[length]):
+            lengths[leaves[i][1]] = length
+            i += 1
+    return lengths
+
+
+def png_canonical_codes(lengths):
+    """RFC 1951 3.2.2: code lengths -> the codes, as integers whose most significant bit (of ``length`` bits) is sent first"""
+    count = [0] * 17
+    for length in lengths:
+        count[length] += 1
+    count[0] = 0
+    code, nxt = 0, [0] * 17
+    for bits in range(1, 16):
+        code = (code + count[bits - 1]) << 1
+        nxt[bits] = code
+    codes = [0] * len(lengths)
+    for s, length in enumerate(lengths):
+        if length:
+            codes[s] = nxt[length]
+            nxt[length] += 1
+    return codes
+
+
+def _png_segment_host(f, final: bool) -> bytes:
+    """one segment of the filtered stream (a numpy uint8 array of 1 .. PNG_SEG bytes) as its deflate bytes"""
+    import numpy as np
+    n = len(f)
+    stored = bytes((int(final), n & 255, n >> 8, ~n & 255, (~n >> 8) & 255)) + f.tobytes()
+    eq = np.zeros(n, dtype=bool)
+    eq[1:] = f[1:] == f[:-1]
+    idx = np.flatnonzero(~eq)                                     # position 0 is one of them
+    run = np.append(idx[1:], n) - idx - 1                         # the stretch of eq behind each
+    full, q = run // 258, run % 258
+    per = 1 + full + np.where(q >= 3, 1, q)                       # tokens per item: its literal, the 258s, the remainder
+    item = np.repeat(np.arange(len(idx)), per)
+    k = np.arange(len(item)) - np.repeat(np.cumsum(per) - per, per)
+    length = np.where((k >= 1) & (k <= full[item]), 258, np.where((k > full[item]) & (q[item] >= 3), q[item], 0))
+    len_sym = np.zeros(259, dtype=np.int64)
+    for i, base in enumerate(_PNG_LEN_BASE):
+        len_sym[base:] = i
+    ls = len_sym[length]
+    is_match = length > 0
+    sym = np.where(is_match, 257 + ls, f[idx][item])
+    hist = np.bincount(sym, minlength=286)
+    hist[256] += 1
+    lengths = png_code_lengths(hist.tolist())
+    codes = png_canonical_codes(lengths)
+    rev = np.array([int(format(c, f'0{l}b')[::-1], 2) if l else 0 for c, l in zip(codes, lengths)], dtype=np.int64)
+    lens = np.array(lengths, dtype=np.int64)
+    eb = np.where(is_match, np.array(_PNG_LEN_EXTRA)[ls], 0)
+    val = rev[sym] | np.where(is_match, (length - np.array(_PNG_LEN_BASE)[ls]) << lens[sym], 0)
+    nbits = lens[sym] + np.where(is_match, eb + 1, 0)             # a match ends with the 1-bit distance code 0
+    dyn_bits = PNG_HEADER_BITS + int(nbits.sum()) + lengths[256] + 3
+    dyn_bytes = (dyn_bits + 7) // 8 + 4
+    if dyn_bytes >= n + 5:
+        return stored
+    rev4 = lambda v: int(format(v, '04b')[::-1], 2)
+    head_val = [0 | 2 << 1 | 29 << 3 | 0 << 8 | 15 << 13] + [0, 0, 0] + [4] * 16 + [rev4(l) for l in lengths] + [rev4(1)]
+    head_bits = [17] + [3] * 19 + [4] * 287
+    val = np.concatenate((np.array(head_val, dtype=np.int64), val, [rev[256], int(final)]))
+    nbits = np.concatenate((np.array(head_bits, dtype=np.int64), nbits, [lengths[256], 3]))
+    at = np.cumsum(nbits) - nbits
+    bits = np.zeros(8 * (dyn_bytes - 4), dtype=np.uint8)
+    for j in range(int(nbits.max())):
+        sel = nbits > j
+        bits[at[sel] + j] = (val[sel] >> j) & 1
+    return np.packbits(bits, bitorder='little').tobytes() + b'\x00\x00\xff\xff'
+
+
+def png_deflate_host(filtered: Tensor, head: Optional[bytes] = None):
+    """the deflate and file stage of csrc/png.hip in numpy: ``filtered`` uint8 [T, L] (any bytes) -> (uint8 [total], int64 [T + 1]) on the CPU, every
+    file = ``head[:33]`` + one IDAT (78 01, the segments, Adler-32) + ``head[33:]``; ``head`` defaults to one grey row of L - 1 pixels"""
+    import struct
+    import zlib
+    t, n = _png_stream(filtered, 'png_deflate_host')
+    head = _png_stream_head(n) if head is None else bytes(head)
+    if len(head) != 45:
+        raise ValueError(f'png_deflate_host: head must be the 45 bytes of _png_head, got {len(head)}')
+    streams = filtered.detach().cpu().contiguous().numpy()
+    out, offsets = bytearray(), [0]
+    for f in streams:
+        z = bytearray(b'\x78\x01')
+        for first in range(0, n, PNG_SEG):
+            z += _png_segment_host(f[first:first + PNG_SEG], first + PNG_SEG >= n)
+        z += struct.pack('>I', zlib.adler32(f.tobytes()))
+        out += head[:33] + _png_chunk(b'IDAT', bytes(z)) + head[33:]
+        offsets.append(len(out))
+    return torch.frombuffer(out, dtype=torch.uint8).clone(), torch.tensor(offsets, dtype=torch.int64)
+
+
+def png_encode_host(frames: Tensor):
+    """``png_encode`` in numpy, on the CPU: (uint8 [total], int64 [T + 1])"""
+    _, h, w, c = _png_frames(frames, 'png_encode_host')
+    return png_deflate_host(png_filter_host(frames), _png_head(h, w, c))
+
+
+def png_filter(frames: Tensor) -> Tensor:
+    """uint8 [T, H (1 + W C)]: the filtered streams of uint8 ``frames`` [T, H, W, C], C = 1 or 3 (the header comment of csrc/png.hip), ``frames`` read
+    in place through its four strides.  ONE launch on the current stream (lp_png_filter).  CPU frames: ``png_filter_host``."""
+    t, h, w, c = _png_frames(frames, 'png_filter')
+    if not frames.is_cuda:
+        return png_filter_host(frames)
+    import ctypes
+    frames = frames.detach()
+    strides = (ctypes.c_longlong * 4)(*frames.stride())
+    n = h * (1 + w * c)
+    with torch.cuda.device(frames.device):
+        if t * n > 2 ** 31 - 1:
+            raise ValueError('png_filter: the filtered streams would exceed 2^31 - 1 bytes: encode fewer frames per call')
+        filtered = torch.empty((t, n), dtype=torch.uint8, device=frames.device)
+        with _Timed('png_filter', 0.0, (t, h, w, c), (2.0 * t * h * w * c, float(t * n))):
+            _jpeg_refusal(_lib.lib().lp_png_filter(frames.data_ptr(), ctypes.addressof(strides), t, h, w, c, filtered.data_ptr(), _stream()),
+                          'lp_png_filter')
+    return filtered
+
+
+def png_deflate(filtered: Tensor, head: Optional[bytes] = None):
+    """(uint8 [total], int64 [T + 1]) on the streams' device: every row of ``filtered`` (uint8 [T, L], any bytes) as a PNG file whose IDAT holds
+    its zlib stream (the header comment of csrc/png.hip); ``head``: the 45 bytes of ``_png_head(H, W, C)``, by default one grey row of L - 1 pixels.
+    Two launches (lp_png_deflate_size), ONE device-to-host copy of one integer -- the total size --, one launch (lp_png_write) into an output
+    allocated at exactly that size.  Bit-identical from run to run.  CPU streams: ``png_deflate_host``."""
+    t, n = _png_stream(filtered, 'png_deflate')
+    head = _png_stream_head(n) if head is None else bytes(head)
+    if len(head) != 45:
+        raise ValueError(f'png_deflate: head must be the 45 bytes of _png_head, got {len(head)}')
+    if not filtered.is_cuda:
+        return png_deflate_host(filtered, head)
+    import ctypes
+    l = _lib.lib()
+    need = l.lp_png_deflate_scratch_bytes(t, n)
+    if need < 0:
+        _jpeg_refusal(int(need), 'lp_png_deflate_scratch_bytes')
+    filtered = filtered.detach().contiguous()
+    dev = filtered.device
+    head_c = (ctypes.c_ubyte * 45)(*head)
+    with torch.cuda.device(dev):
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(t + 1, dtype=torch.int64, device=dev)
+        with _Timed('png_deflate_size', 0.0, (t, n), (float(t * n), float(need))):
+            _jpeg_refusal(l.lp_png_deflate_size(filtered.data_ptr(), t, n, scratch.data_ptr(), need, offsets.data_ptr(), _stream()),
+                          'lp_png_deflate_size')
+        total = int(offsets[t].item())                                  # the one read-back
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        with _Timed('png_write', 0.0, (t, n), 2.0 * total):
+            _jpeg_refusal(l.lp_png_write(scratch.data_ptr(), need, t, n, ctypes.addressof(head_c), offsets.data_ptr(), out.data_ptr(), total,
+                                         _stream()), 'lp_png_write')
+    return out, offsets
+
+
+def png_encode(frames: Tensor):
+    """(uint8 [total], int64 [T + 1]) on the frames' device: uint8 ``frames`` [T, H, W, C], C = 1 or 3 (any strides: what ``drive.drive_frames``
+    returns) as T complete PNG files back to back, file t = bytes offsets[t] .. offsets[t + 1], every pixel kept exactly (the header comment of
+    csrc/png.hip).  ``png_filter`` + ``png_deflate``: four launches and one read-back of one integer.  CPU frames: ``png_encode_host``."""
+    _, h, w, c = _png_frames(frames, 'png_encode')
+    if not frames.is_cuda:
+        return png_encode_host(frames)
+    return png_deflate(png_filter(frames), _png_head(h, w, c))
+
+
 # ---- baseline JPEG decode of the loader's frames (csrc/jpeg_decode.hip holds the definition) ---------------------------------------------------------
 class JpegDecoded(NamedTuple):
     """``buf`` uint8: frame f = dense [H, W, 3] RGB at ``offsets[f]``; ``status`` int32 [N] on the buffer's device (0 ok, 1 no code matches, 2 a run

@@ -179,12 +179,20 @@ def sheet(data, n_samples=2, captions=True):
     return ops.visual_sheet(panels, caption=strip)
 
 
-def save_png(path, sheet_u8):
-    """one device-to-host copy of the uint8 HWC sheet, then PIL writes the PNG (lossless: the file decodes to the same bytes)"""
+def save_png(path, sheet_u8, encoder='pil'):
+    """one device-to-host copy of the uint8 HWC sheet, then PIL writes the PNG (lossless: the file decodes to the same bytes).  ``encoder='gpu'``:
+    the sheet is encoded where it is (``hipops.png_encode``, csrc/png.hip) and only the file's bytes are copied; it decodes to the same bytes too"""
     import os
     from PIL import Image
     if not (isinstance(sheet_u8, torch.Tensor) and sheet_u8.dtype == torch.uint8 and sheet_u8.dim() == 3 and sheet_u8.shape[2] == 3):
         raise ValueError('save_png: expected a uint8 tensor [H, W, 3]')
+    if encoder not in ('pil', 'gpu'):
+        raise ValueError(f"save_png: encoder must be 'pil' or 'gpu', got {encoder!r}")
     os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+    if encoder == 'gpu':
+        data, _ = ops.png_encode(sheet_u8[None])
+        with open(str(path), 'wb') as f:
+            f.write(data.cpu().numpy().tobytes())
+        return path
     Image.fromarray(sheet_u8.cpu().numpy()).save(str(path))
     return path

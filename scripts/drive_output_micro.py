@@ -2,7 +2,8 @@
 """The drive loop WITH its output route, in frames/s, for each ``drive.py --format``: the full-size nets of ``bench.py``'s drive measurement
 (MobileNetV2 pose encoder + generator at 256 x 256, fine-tuned form, eval mode, random weights), ``drive.drive_frames`` called eagerly on batches of
 B driving frames resident on the device, as ``drive.main`` does, then the sequence written to a temporary directory: npy (``torch.cat(...).cpu()`` +
-``np.save``), png (that copy + ``write_png_frames``), avi (``write_avi``: JPEG on the GPU, the compressed bytes to the host, the container).  The
+``np.save``), png (that copy + ``write_png_frames``), avi (``write_avi``: JPEG on the GPU, the compressed bytes to the host, the container),
+png with ``--png_encoder gpu`` (``write_png_frames_gpu``: PNG on the GPU, the compressed bytes to the host, one file per frame).  The
 host clock around a whole sequence, a synchronisation at either end; one warm-up sequence, then ``--reps`` timed: median, min ... max.  The npy and
 png routes are the code of the commit before ``--format avi`` existed, unchanged.  Needs the MI355X."""
 import argparse
@@ -47,6 +48,8 @@ def main():
             frames.append(drive.drive_frames(E, G, {'pose_input_rgbs': driver[:batch]}))
         if fmt == 'avi':
             drive.write_avi(os.path.join(tmp, 'out.avi'), torch.cat(frames), 25, 90)
+        elif fmt == 'png-gpu':
+            drive.write_png_frames_gpu(os.path.join(tmp, 'png_gpu'), torch.cat(frames))
         elif fmt == 'none':
             torch.cat(frames)
         else:
@@ -59,7 +62,7 @@ def main():
     with torch.no_grad():
         driver = torch.rand(8, 1, 3, 256, 256, device='cuda:0')
         for batch in (1, 8):
-            for fmt in ('none', 'npy', 'avi', 'png'):
+            for fmt in ('none', 'npy', 'avi', 'png-gpu', 'png'):
                 total = a.png_frames if fmt == 'png' else a.frames
                 sequence(fmt, batch, total)
                 times = []
@@ -70,7 +73,7 @@ def main():
                     torch.cuda.synchronize()
                     times.append(time.perf_counter() - t0)
                 fps = sorted(total / t for t in times)
-                what = 'no output (the frames stay on the device)' if fmt == 'none' else f'--format {fmt}'
+                what = {'none': 'no output (the frames stay on the device)', 'png-gpu': '--format png --png_encoder gpu'}.get(fmt, f'--format {fmt}')
                 print(f'[drive_output_micro] B = {batch}, {total} frames, {what}: median {statistics.median(fps):.0f} frames/s, '
                       f'min {fps[0]:.0f} ... max {fps[-1]:.0f} ({len(times)} timed)', flush=True)
     for name in ('out.avi', 'out.npy'):
