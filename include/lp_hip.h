@@ -29,6 +29,19 @@ extern "C" {
 const char* lp_last_error(void);
 int lp_abi_version(void);
 
+/* Diagnostic (additive; the ABI version stays): the form that the dispatchers of lp_conv16_fwd(_stats) / lp_conv16_wgrad (and the grouped entry points
+ * that share their launchers) chose for the CALLING THREAD's last launch, copied into out[0 .. 19] (HOST ints; capacity >= 20, else LP_ERR_ARG; all
+ * zero before any launch).  Written by the host launch functions after their decisions; no kernel reads it.  Tests assert the form their ids name.
+ *   out[0]  0 nothing launched yet | 1 convolution | 2 weight gradient;     out[19] precision mode
+ *   convolution:     out[1] kernel 1 conv_dma | 2 conv_pipe | 3 conv1x1_pipe;  [2] KS (2: phase form)  [3] fused upsampling  [4] WM  [5] WN  [6] MR  [7] NR
+ *                    (WM x WN waves of MR x NR MFMA tiles)  [8] channels per chunk  [9] ping-pong  [10] weight buffers (ring depth)  [11] split-K factor
+ *                    [12] double-buffered activations  [13] norm statistics offered  [14] split-K finish launched  [15] workgroups along the tile axis
+ *                    [16] [17] [18] log2 of tile height, width, images per tile
+ *   weight gradient: out[1] kernel 1 conv_wgrad | 2 wgrad1x1 | 3 wgrad3_pipe;  [2] KS  [3] upsampled input  [4] output channels per workgroup
+ *                    [5] splits actually used  [6] reduction 1 tiled | 2 flat, 32 outputs per block | 3 flat, 256  (0: none, grouped form)
+ *                    [7] bias gradient  [8] pixel tiles (1x1 kernel: stages)  [9] [10] [11] log2 of tile height, width, image slots per tile */
+int lp_last_launch_form(int* out, int capacity);
+
 /* Re-layout + 16-bit conversion of a conv/linear weight.  w: fp32 [Cout][Cin][T] (reference nn.Conv2d layout, T = k*k).
  * mode 0 (forward):  out[t][co][ci] = w[co][ci][t]            rows padded to CoutP (x128), cols to CinP (x32)
  * mode 1 (dgrad):    out[T-1-t][ci][co] = w[co][ci][t]        rows = Cin padded to RowsP, cols = Cout padded to ColsP

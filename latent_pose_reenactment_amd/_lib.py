@@ -20,6 +20,7 @@ _vp, _i, _f, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longl
 SIGNATURES = {
     'lp_last_error': (ctypes.c_char_p, []),
     'lp_abi_version': (_i, []),
+    'lp_last_launch_form': (_i, [_vp, _i]),
     'lp_pack_weights': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'lp_pack_desc_bytes': (_i, []),
     'lp_pack_weights_batch': (_i, [_vp, _i, _ll, _vp]),

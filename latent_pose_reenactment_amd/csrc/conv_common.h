@@ -225,6 +225,7 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Params& p, f32x4_t (
                     if (p.bias) v += p.bias[co];
                     if (p.res) v += p.res[rpix + co];
                     if (p.mask16 && !((unsigned)(p.mask16[pixi * p.Co8 + co] - 1u) < 0x7fffu)) v = 0.f;
+                    if (p.o_relu & 2) v = fmaxf(v, 0.f);      // (y itself stored as relu(y), as in the coalesced path and in splitk_reduce_kernel)
                     if (p.y) p.y[pix + co] = v;
                     am_s = fmaxf(am_s, fabsf(v));
                     if (p.o_hi) {

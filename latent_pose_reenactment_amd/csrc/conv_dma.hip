@@ -29,6 +29,7 @@
 #include "conv_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
+#include "lp_launch_form.h"
 #include <type_traits>
 
 __device__ __attribute__((aligned(64))) unsigned int lp_zero_page[16];      // what out-of-image / out-of-channel DMA lanes read
@@ -405,6 +406,7 @@ static int launch_v(Conv16Params& p, size_t lds, dim3 grid, hipStream_t stream) 
             return lp_set_error(LP_ERR_HIP, "hipFuncSetAttribute failed");
         attr_dev = dev;
     }
+    lp_form_conv(LP_FORM_CONV_DMA, PREC, KS, UPS, WM, WN, MR, NR, CC, PP, NBUF, p);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64 * (PP ? 2 : 1)), lds, stream, p);
     return lp_check_launch("conv_dma");
 }
@@ -619,6 +621,7 @@ extern "C" int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, c
         else hipLaunchKernelGGL(splitk_reduce_kernel<LP_PREC_F16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
         rc = lp_check_launch("splitk_reduce");
         if (rc) return rc;
+        lp_form_record()[LP_FC_FINISH] = 1;
     }
     if (stats_rows) *stats_rows = p.stats_rows;
     // channel counts the epilogue writes element-wise (Cout % 8 != 0: padding channels) get their 16-bit planes from a

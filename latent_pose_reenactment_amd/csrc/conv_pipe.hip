@@ -23,6 +23,7 @@
 #include "conv_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
+#include "lp_launch_form.h"
 
 static __device__ __attribute__((aligned(64))) unsigned int lp_zero_page_pipe[16];      // what out-of-image DMA lanes read
 
@@ -408,6 +409,7 @@ static int launch_pipe1x1(Conv16Params& p, hipStream_t stream) {
         attr_dev = dev;
     }
     p.xcd_map = 0; p.ntiles = tiles; p.nco = (p.Cout + BN - 1) / BN;
+    lp_form_conv(LP_FORM_CONV_PIPE1X1, PREC, 1, 0, WM, WN, 4, 4, 32, 0, R, p);
     hipLaunchKernelGGL(kern, dim3(tiles, (p.Cout + BN - 1) / BN), dim3(256), lds, stream, p);
     const int rc = lp_check_launch("conv1x1_pipe");
     return rc ? rc : 1;
@@ -476,6 +478,7 @@ static int launch_pipe(Conv16Params& p, hipStream_t stream) {
         attr_dev = dev;
     }
     const dim3 grid = conv16_grid(p, tiles, (p.Cout + BN - 1) / BN);          // (sets p.xcd_map / ntiles / nco: BEFORE p is copied into the launch)
+    lp_form_conv(LP_FORM_CONV_PIPE, PREC, 3, UPS, WM, WN, MR, NR, 32, 0, 3, p);
     hipLaunchKernelGGL(kern, grid, dim3(NWAVE * 64), lds, stream, p);
     const int rc = lp_check_launch("conv_pipe");
     return rc ? rc : 1;

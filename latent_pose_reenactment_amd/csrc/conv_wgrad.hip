@@ -12,6 +12,7 @@
 #include "lp_common.h"
 #include "lp_hip.h"
 #include "lp_internal.h"
+#include "lp_launch_form.h"
 
 struct WgradParams {
     const uint16_t* a_hi; const uint16_t* a_lo; const uint16_t* d_hi; const uint16_t* d_lo; float* part;
@@ -471,6 +472,7 @@ static int launch_wgrad(WgradParams& p, float* dw, float* dbias, const float* ou
         attr_dev = dev;
     }
     dim3 grid(p.splits, (p.CoP + COB - 1) / COB, p.diag ? 1 : p.CiP / 64);
+    lp_form_wgrad(LP_FORM_WGRAD_GENERIC, PREC, KS, UPS, COB, p.num_tiles, lth, ltw, lnb, p);
     hipLaunchKernelGGL(kern, grid, dim3(COB * 4), lds, stream, p);
     int rc = lp_check_launch("conv_wgrad");
     if (rc) return rc;
@@ -631,6 +633,7 @@ static int launch_wreduce(const WgradParams& p, int T, float* dw, float* dbias, 
                           hipStream_t stream) {
     const int bblocks = p.bpart ? (p.Cout + 63) / 64 : 0;
     const int wblocks = wred_blocks(p.Cin, p.Cout, T);
+    lp_form_record()[LP_FW_RED] = wred_tiled(p.Cin, p.Cout) ? LP_FORM_WRED_TILED : wred_flat_out(p.Cin, p.Cout, T) == 32 ? LP_FORM_WRED_FLAT32 : LP_FORM_WRED_FLAT256;
     if (wred_tiled(p.Cin, p.Cout))
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wblocks + bblocks), dim3(256), 0, stream, p.part, dw, p.splits, T, p.Cout, p.Cin, p.CoP, p.CiP,
                            p.bpart, dbias, wblocks, out_scale, sn_w, sn_dot, p.db_acc);
@@ -667,6 +670,7 @@ static int launch_wgrad1x1(WgradParams& p, float* dw, const float* out_scale, co
             return lp_set_error(LP_ERR_HIP, "hipFuncSetAttribute failed");
         attr_dev = dev;
     }
+    lp_form_wgrad(LP_FORM_WGRAD_1X1, PREC, 1, 0, 128, q.nstage, 0, 0, 0, p);
     hipLaunchKernelGGL(kern, dim3((unsigned)(q.tiles_co * q.tiles_ci * splits)), dim3(256), lds, stream, q);
     int rc = lp_check_launch("wgrad1x1");
     if (rc) return rc;
@@ -905,6 +909,7 @@ static int launch_wgrad3_pipe(WgradParams& p, float* dw, float* dbias, const flo
             return lp_set_error(LP_ERR_HIP, "hipFuncSetAttribute failed");
         attr_dev = dev;
     }
+    lp_form_wgrad(LP_FORM_WGRAD_PIPE3, PREC, 3, UPS, 64, q.num_tiles, 3, 4, 0, p);
     hipLaunchKernelGGL(kern, dim3((unsigned)(ntile * splits)), dim3(256), lds, stream, q);
     int rc = lp_check_launch("wgrad3_pipe");
     if (rc) return rc;

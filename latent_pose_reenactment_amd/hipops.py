@@ -344,7 +344,32 @@ def conv16(a: Act16, pack: WeightPack, *, ksize: int, upsample: bool = False, bi
     return out[0] if len(out) == 1 else out
 
 
-_THIN = os.environ.get('LP_THIN', '1') != '0'      # LP_THIN=0: thin-channel layers through the MFMA kernels (test knob)
+_FORM_CONV = ('what', 'kernel', 'ks', 'ups', 'wm', 'wn', 'mr', 'nr', 'cc', 'pp', 'nbuf', 'ksplit', 'a_dbuf', 'stats', 'finish', 'tiles', 'lth', 'ltw', 'lnb')
+_FORM_WGRAD = ('what', 'kernel', 'ks', 'ups', 'cob', 'splits', 'red', 'bias', 'tiles', 'lth', 'ltw', 'lnb')
+_FORM_KERNEL = {1: {1: 'dma', 2: 'pipe', 3: 'pipe1x1'}, 2: {1: 'generic', 2: '1x1', 3: 'pipe3'}}
+_FORM_RED = {0: None, 1: 'tiled', 2: 'flat32', 3: 'flat256'}
+
+
+def last_launch_form() -> dict:
+    """the form the conv / weight-gradient dispatcher chose for this thread's last launch (lp_last_launch_form, include/lp_hip.h) as a dict:
+    ``what`` None | 'conv' | 'wgrad', ``kernel`` by name, the slots by name, ``prec``.  A diagnostic for tests: host state only, nothing is synchronised."""
+    import ctypes
+    rec = (ctypes.c_int * 20)()
+    check(_lib.lib().lp_last_launch_form(ctypes.addressof(rec), 20), 'lp_last_launch_form')
+    v = list(rec)
+    if v[0] == 0:
+        return {'what': None}
+    names = _FORM_CONV if v[0] == 1 else _FORM_WGRAD
+    d = dict(zip(names, v))
+    d['what'] = 'conv' if v[0] == 1 else 'wgrad'
+    d['kernel'] = _FORM_KERNEL[v[0]][v[1]]
+    d['prec'] = v[19]
+    if v[0] == 2:
+        d['red'] = _FORM_RED[d['red']]
+    return d
+
+
+_THIN = os.environ.get('LP_THIN', '1') != '0'     # LP_THIN=0: thin-channel layers through the MFMA kernels (test knob)
 _THIN_MFMA = os.environ.get('LP_THIN_MFMA', '1') != '0'
 
 

@@ -99,9 +99,10 @@ def stats_words(cs, cout):
 
 # ---- wide convs: lp_conv16_fwd(_stats) through act_pack + pack_weights + conv16 ---------------------------------------------------------------
 def conv_entry(name, n, h, w, cin, cout, k, *, precs=(0, 1, 2), form='plain', bias=False, res_shift=None, out16=None, want_y=True, stats=False,
-               relu_mask=False, amax=False, small_k=False, mode=0, y_relu=False, covered=None):
+               relu_mask=False, amax=False, small_k=False, mode=0, y_relu=False, covered=None, expect=None):
     """(n, h, w) = the OUTPUT map of the launch; form: plain | up (fused x2 upsample) | phase (mode-2 pack) | phase_dgrad (mode-3) | pool (mode-4
-    pack, conv + AvgPool2d(2)) | pool_dgrad (mode-5); ``covered`` (with ``stats``): whether the epilogue's fused statistics cover the geometry -- asserted"""
+    pack, conv + AvgPool2d(2)) | pool_dgrad (mode-5); ``covered`` (with ``stats``): whether the epilogue's fused statistics cover the geometry -- asserted;
+    ``expect``: fields of the launch record (hipops.last_launch_form) that the form named by the entry must show (a value, or a predicate) -- asserted"""
     assert not stats or covered is not None
     for prec in precs:
         def make(prec=prec):
@@ -128,6 +129,9 @@ def conv_entry(name, n, h, w, cin, cout, k, *, precs=(0, 1, 2), form='plain', bi
                 out = ops.conv16(a, pk, ksize=k, upsample=form in ('up', 'phase', 'pool_dgrad'), bias=bias, res=res, res_shift=res_shift or 0, alpha=alpha,
                                  prec=prec, relu_mask=m16, out16=out16, amax=amax, stats=stats, want_y=want_y, phase=form in ('phase', 'pool_dgrad'),
                                  phase_dgrad=form in ('phase_dgrad', 'pool'), y_relu=y_relu)
+                rec = ops.last_launch_form()
+                for key, want in (expect or {}).items():
+                    assert want(rec[key]) if callable(want) else rec[key] == want, f'the entry names a form that did not run: {key} = {rec[key]} in {rec}'
                 out = list(out) if isinstance(out, tuple) else [out]
                 r = {'planes': a, 'pack': pk, 'mask16': m16, 'slots': slots_of(out[0]) if out[0] is not None else None}
                 if stats:
@@ -140,29 +144,30 @@ def conv_entry(name, n, h, w, cin, cout, k, *, precs=(0, 1, 2), form='plain', bi
 
 
 conv_entry('plain', 2, 8, 8, 64, 128, 3)
-conv_entry('1x1 cout 24', 2, 16, 16, 128, 24, 1)
-conv_entry('split-K workspace residual', 8, 4, 4, 64, 64, 3, res_shift=0)
-conv_entry('fused upsample res_shift 1', 2, 8, 8, 64, 192, 3, form='up', res_shift=1)
-conv_entry('narrow output bias', 2, 32, 32, 64, 4, 3, bias=True)
+conv_entry('1x1 cout 24', 2, 16, 16, 128, 24, 1, expect=dict(ks=1))
+SPLITS = dict(ksplit=lambda v: v > 1, finish=1)          # (a slice needs >= 2 chunks of 32 input channels: 64 channels do not split)
+conv_entry('split-K workspace residual', 8, 4, 4, 128, 64, 3, res_shift=0, expect=SPLITS)
+conv_entry('fused upsample res_shift 1', 2, 8, 8, 64, 192, 3, form='up', res_shift=1, expect=dict(ks=3, ups=1))
+conv_entry('narrow output bias', 2, 32, 32, 64, 4, 3, bias=True, expect=dict(wn=1, nr=1))
 conv_entry('small-K pack', 1, 32, 32, 16, 8, 3, small_k=True)
-conv_entry('masked last group H != W', 3, 8, 16, 64, 128, 3)
+conv_entry('masked last group H != W', 3, 8, 16, 64, 128, 3, expect=dict(tiles=3))          # (an odd number of tiles)
 conv_entry('data-gradient pack', 2, 8, 8, 64, 128, 3, mode=1)
-conv_entry('phase up', 3, 8, 8, 96, 136, 3, form='phase', bias=True)
-conv_entry('phase up statistics not covered', 4, 8, 8, 32, 32, 3, form='phase', out16=0, stats=True, covered=False)
-conv_entry('phase dgrad', 3, 4, 4, 136, 96, 3, form='phase_dgrad')
-conv_entry('conv+pool', 3, 8, 12, 64, 128, 3, form='pool', bias=True, res_shift=0, out16=1, y_relu=True, precs=(1, 2))
-conv_entry('conv+pool dgrad', 3, 16, 24, 128, 64, 3, form='pool_dgrad', precs=(1, 2))
+conv_entry('phase up', 3, 8, 8, 96, 136, 3, form='phase', bias=True, expect=dict(ks=2))          # (KS = 2: the phase forms' 2 x 2 taps)
+conv_entry('phase up statistics not covered', 4, 8, 8, 32, 32, 3, form='phase', out16=0, stats=True, covered=False, expect=dict(ks=2, stats=0))
+conv_entry('phase dgrad', 3, 4, 4, 136, 96, 3, form='phase_dgrad', expect=dict(ks=2))
+conv_entry('conv+pool', 3, 8, 12, 64, 128, 3, form='pool', bias=True, res_shift=0, out16=1, y_relu=True, precs=(1, 2), expect=dict(ks=2))
+conv_entry('conv+pool dgrad', 3, 16, 24, 128, 64, 3, form='pool_dgrad', precs=(1, 2), expect=dict(ks=2))
 conv_entry('out planes', 2, 8, 8, 64, 128, 3, out16=1, bias=True)
 conv_entry('out planes cout 20', 2, 8, 8, 64, 20, 3, out16=0)
 conv_entry('planes only', 2, 8, 8, 64, 128, 3, out16=1, want_y=False)
-conv_entry('statistics covered', 8, 16, 16, 128, 64, 1, stats=True, precs=(1, 2), covered=True)
-conv_entry('statistics 3x3', 5, 16, 32, 64, 192, 3, stats=True, precs=(1, 2), covered=True)
-conv_entry('statistics not covered', 1, 8, 8, 256, 128, 3, stats=True, precs=(1, 2), covered=False)
+conv_entry('statistics covered', 8, 16, 16, 128, 64, 1, stats=True, precs=(1, 2), covered=True, expect=dict(ks=1, stats=1))
+conv_entry('statistics 3x3', 5, 16, 32, 64, 192, 3, stats=True, precs=(1, 2), covered=True, expect=dict(ks=3, stats=1))
+conv_entry('statistics not covered', 1, 8, 8, 256, 128, 3, stats=True, precs=(1, 2), covered=False, expect=dict(stats=0))
 conv_entry('statistics planes only', 2, 16, 16, 64, 64, 3, stats=True, out16=1, want_y=False, precs=(1, 2), covered=True)
 conv_entry('relu_mask', 2, 8, 8, 64, 128, 3, relu_mask=True, mode=1)
 conv_entry('relu_mask cout 20', 2, 8, 8, 64, 20, 3, relu_mask=True, mode=1)
 conv_entry('amax slots', 2, 8, 8, 64, 128, 3, amax=True, mode=1, precs=(2,))
-conv_entry('amax slots split-K', 8, 4, 4, 64, 64, 3, amax=True, mode=1, precs=(2,))
+conv_entry('amax slots split-K', 8, 4, 4, 128, 64, 3, amax=True, mode=1, precs=(2,), expect=SPLITS)
 
 
 # ---- lp_conv16_wgrad ---------------------------------------------------------------------------------------------------------------------------

@@ -55,7 +55,7 @@ def act_ref(x, pro, scale, shift, ups):
 CONV_CASES = [
     # N, H(out), W, Cin, Cout, ks, ups, pro, bias, res_shift(-1 none)
     (2, 8, 8, 64, 128, 3, 0, 1, 0, -1),
-    (8, 4, 4, 64, 64, 3, 0, 1, 0, 0),
+    (8, 4, 4, 64, 64, 3, 0, 1, 0, 0),           # one tile, residual; two 32-channel chunks do NOT split (a slice needs >= 2): split-K is held by tests/conv_dma_cases.py
     (3, 4, 4, 128, 256, 3, 0, 1, 0, -1),
     (1, 16, 16, 128, 64, 3, 1, 1, 0, -1),
     (2, 8, 8, 64, 192, 3, 1, 1, 0, 1),
@@ -69,7 +69,8 @@ CONV_CASES = [
     (2, 64, 64, 64, 64, 3, 0, 1, 0, -1),
     (2, 20, 12, 3, 128, 1, 0, 0, 1, -1),      # direct fp32 kernel for <= 4 input channels: 1x1, odd image size
     (3, 12, 20, 3, 64, 3, 0, 0, 1, -1),
-    (3, 8, 16, 64, 128, 3, 0, 1, 1, -1),        # 3 tiles: with the ping-pong schedule the last workgroup's second group is masked
+    (3, 8, 16, 64, 128, 3, 0, 1, 1, -1),        # 3 tiles of the 8-wave form (<= 256 pixels, Cout > 64), which has no ping-pong schedule: the masked second
+                                                # group of an odd tile count is held by tests/conv_dma_cases.py ('pp 3x8x16 64->64') under LP_CONV_PP=1
     (5, 16, 16, 64, 64, 3, 0, 2, 1, 0),         # 5 tiles of 256 pixels (Cout <= 64 tile), residual
 ]
 
