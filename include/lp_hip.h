@@ -129,6 +129,16 @@ int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, const uint16
                         int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
                         uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
                         float* stats, long long stats_capacity_floats, int* stats_rows, void* stream);
+/* lp_conv16_fwd_stats with a GATED residual: res_bits [P][Cout / 8] | NULL, one byte per (pixel, 8-channel group), bit j = channel 8 g + j (as
+ * lp_bn_add_act_bits writes them): y += res where the bit is set and += 0 where it is clear -- a select, so a NaN of res under a cleared bit
+ * does not reach y.  Needs res, res_shift == 0, Cout % 8 == 0 and ksize == 1 (other kernel sizes: LP_ERR_UNSUPPORTED).  The data gradient of a residual block's first conv adds the skip gradient
+ * d_out * [out > 0] from d_out itself this way: no masked fp32 copy of d_out is written or read. */
+int lp_conv16_fwd_gated(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo, float* y,
+                        const float* bias, const float* res, const unsigned char* res_bits, const float* alpha, const float* alpha2,
+                        int N, int H, int W, int Cin, int Cout, int CinP, int CoutP,
+                        int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
+                        uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
+                        float* stats, long long stats_capacity_floats, int* stats_rows, void* stream);
 long long lp_conv16_stats_floats(int N, int H, int W, int Cout);
 int lp_norm_stats_finalize(const float* part, int S, const float* gamma, const float* beta, int ab_stride, float eps, float momentum,
                            float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
@@ -320,6 +330,17 @@ int lp_bn_add_act_planes(const float* y, const float* scale, const float* shift,
 int lp_bn_add_act16(const uint16_t* y16, const float* scale, const float* shift, const float* res, const float* res_scale,
                     const float* res_shift, float* out, uint16_t* hi, long long P, int C, int relu, void* stream);
 int lp_bn_act16(const uint16_t* y16, const float* scale, const float* shift, uint16_t* out_hi, long long P, int C, int relu, void* stream);
+/*   lp_bn_add_act_bits / lp_bn_add_act_planes_bits / lp_bn_add_act16_bits: the three forms above that also leave the ReLU pattern of the block
+ *                     output as ONE BIT per element: bits [P][C / 8] | NULL, one byte per (pixel, 8-channel group), bit j = channel 8 g + j, set
+ *                     where the HI plane word the kernel stores is > 0 (sign clear, magnitude non-zero: a positive value that rounds to zero in
+ *                     the plane gives 0, a NaN gives 1 -- the predicate of lp_bn_bwd16_h's mask mode 3).  bits needs hi.  Read by
+ *                     lp_bn_bwd16_h / lp_bn_bwd16_dual (mask mode 4) and lp_conv16_fwd_gated. */
+int lp_bn_add_act_bits(const float* y, const float* scale, const float* shift, const float* res, const float* res_scale, const float* res_shift,
+                       float* out, uint16_t* hi, uint16_t* lo, unsigned char* bits, long long P, int C, int relu, int prec, void* stream);
+int lp_bn_add_act_planes_bits(const float* y, const float* scale, const float* shift, const uint16_t* res_hi, const uint16_t* res_lo, float* out,
+                              uint16_t* hi, uint16_t* lo, unsigned char* bits, long long P, int C, int relu, int prec, void* stream);
+int lp_bn_add_act16_bits(const uint16_t* y16, const float* scale, const float* shift, const float* res, const float* res_scale,
+                         const float* res_shift, float* out, uint16_t* hi, unsigned char* bits, long long P, int C, int relu, void* stream);
 /*   The generator's 16-bit-resident conv outputs (round 5; fp16 mode: no fp32 copy of a conv output between the AdaIN blocks):
  *   lp_adain_act16:      out_hi = fp16((relu?)(y16[n]*scale[n][c]+shift[n][c])), per-IMAGE affines [N][C] -- AdaptiveNorm2d + ReLU
  *                        (generators/common/blocks.py:18-26,70-73) as the prologue of the next conv, 2 B read + 2 B written per element
@@ -351,6 +372,17 @@ int lp_bn_bwd16_h(const float* dA, const float* x, const uint16_t* x16, const vo
                   const float* rstd, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo, float* out_scale,
                   float* dgamma, float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats, int prec,
                   float* g_out, void* stream);
+/*   mask mode 4 (lp_bn_bwd16_h, lp_bn_bwd16_dual): mask_src = the pattern of mode 3 as one bit per element, bytes [P][C / 8] from lp_bn_add_act_bits.
+ *   lp_bn_bwd16_dual: TWO BatchNorm backwards over the same incoming gradient dA and the same pattern in one pass pair: out = relu(BN_a(xa) +
+ *                     BN_b(xb)), bn3 and the downsample BatchNorm of a residual block's first bottleneck.  Per BN the arguments and results of
+ *                     lp_bn_bwd16_h, each with its own workspace of lp_bn_bwd16_workspace_bytes(P, C); every result is bit-identical to two
+ *                     lp_bn_bwd16_h calls, dA and the pattern are read once per pass.  xa / xb: both fp32 (x?16 NULL) or both fp16 planes (x? NULL);
+ *                     mask_mode 1 .. 4 (a pattern that does not depend on x). */
+int lp_bn_bwd16_dual(const float* dA, const void* mask_src, const float* xa, const uint16_t* xa16, const float* gamma_a, const float* mean_a,
+                     const float* rstd_a, uint16_t* hi_a, uint16_t* lo_a, float* out_scale_a, float* dgamma_a, float* dbeta_a,
+                     float* workspace_a, const float* xb, const uint16_t* xb16, const float* gamma_b, const float* mean_b,
+                     const float* rstd_b, uint16_t* hi_b, uint16_t* lo_b, float* out_scale_b, float* dgamma_b, float* dbeta_b,
+                     float* workspace_b, long long P, int C, int mask_mode, int frozen_stats, int prec, void* stream);
 int lp_spatial_mean_fwd(const float* x, float* out, int N, int HW, int C, void* stream);
 int lp_spatial_mean_bwd(const float* g, float* dx, int N, int HW, int C, void* stream);
 

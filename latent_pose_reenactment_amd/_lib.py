@@ -34,6 +34,7 @@ SIGNATURES = {
     'lp_conv16_fwd': (_i, [_vp] * 9 + [_i] * 11 + [_vp, _vp, _vp, _i, _vp, _ll, _vp, _vp]),
     'lp_conv16_fwd_workspace_bytes': (_ll, [_i] * 5),
     'lp_conv16_fwd_stats': (_i, [_vp] * 9 + [_i] * 11 + [_vp, _vp, _vp, _i, _vp, _ll, _vp, _vp, _ll, _vp, _vp]),
+    'lp_conv16_fwd_gated': (_i, [_vp] * 10 + [_i] * 11 + [_vp, _vp, _vp, _i, _vp, _ll, _vp, _vp, _ll, _vp, _vp]),
     'lp_conv16_stats_floats': (_ll, [_i] * 4),
     'lp_norm_stats_finalize': (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'lp_gconv16_fwd_stats': (_i, [_vp] * 6 + [_i] * 6 + [_vp, _vp, _ll, _vp, _vp]),
@@ -80,6 +81,9 @@ SIGNATURES = {
     'lp_bn_add_act': (_i, [_vp] * 9 + [_ll, _i, _i, _i, _vp]),
     'lp_bn_add_act_planes': (_i, [_vp] * 8 + [_ll, _i, _i, _i, _vp]),
     'lp_bn_add_act16': (_i, [_vp] * 8 + [_ll, _i, _i, _vp]),
+    'lp_bn_add_act_bits': (_i, [_vp] * 10 + [_ll, _i, _i, _i, _vp]),
+    'lp_bn_add_act_planes_bits': (_i, [_vp] * 9 + [_ll, _i, _i, _i, _vp]),
+    'lp_bn_add_act16_bits': (_i, [_vp] * 9 + [_ll, _i, _i, _vp]),
     'lp_bn_act16': (_i, [_vp] * 4 + [_ll, _i, _i, _vp]),
     'lp_adain_act16': (_i, [_vp] * 4 + [_i, _ll, _i, _i, _vp]),
     'lp_adain_relu_bwd16': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -90,6 +94,7 @@ SIGNATURES = {
     'lp_bn_bwd16_workspace_bytes': (_ll, [_ll, _i]),
     'lp_bn_bwd16': (_i, [_vp] * 14 + [_ll, _i, _i, _f, _i, _i, _vp, _vp]),
     'lp_bn_bwd16_h': (_i, [_vp] * 15 + [_ll, _i, _i, _f, _i, _i, _vp, _vp]),
+    'lp_bn_bwd16_dual': (_i, [_vp] * 24 + [_ll, _i, _i, _i, _i, _vp]),
     'lp_spatial_mean_fwd': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'lp_spatial_mean_bwd': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'lp_dwconv3x3_dgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

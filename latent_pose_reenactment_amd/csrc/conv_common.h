@@ -33,6 +33,10 @@ struct Conv16Params {
                                   // [4 phases][2 x 2 taps][CoutP][CinP]; the epilogue writes to the phase's position of the H x W output
     int grouped;                  // block-diagonal (grouped) conv: the workgroup's 64 output channels only see input channels co0 .. co0+63;
                                   // the weight image then has 64 columns (CinP = 64) and the activation channel offset is co0
+    const unsigned char* res_bits = nullptr;      // NULL | one bit per element of `res` ([P][Cout / 8] bytes, bit j = channel 8 g + j; Cout % 8 == 0, res_shift 0):
+                                  // the residual term is res where the bit is set and 0 elsewhere (a select: a NaN under a cleared bit adds 0) --
+                                  // the ReLU pattern of a residual block's output gating the skip gradient, with no masked fp32 copy of it.
+                                  // Read by the GATE instantiations of the epilogue only: the 1x1 forms of conv_dma_kernel (the host refuses the rest)
 };
 
 static inline int ilog2_floor(int v) { int l = 0; while ((1 << (l + 1)) <= v) ++l; return l; }
@@ -80,8 +84,9 @@ int lp_gconv_rows_launch(Conv16Params& p, int group_size, int prec, hipStream_t 
 // group (row block of the statistics partials = tile_index * WM + wm).  MRP = MFMA row blocks transposed through LDS at a time (the scratch
 // is waves x MRP*16 x (NR*16+4) floats at the start of `smem`, which must be dead: the function begins with a workgroup barrier).
 // y = acc*alpha*alpha2 + bias + res[n, y>>rs, x>>rs], ReLU-mask from 16-bit planes, optional fp32 y, operand planes of (relu?)(y), amax,
-// {count, mean, M2} partials, or the raw split-K partial tile.  Must be called by every wave of the workgroup.
-template <int WM, int WN, int MR, int NR, int PREC, int MRP>
+// {count, mean, M2} partials, or the raw split-K partial tile.  Must be called by every wave of the workgroup.  GATE: the residual is gated by
+// p.res_bits (non-NULL then; coalesced path) -- a template flag, so that the kernels that never see a gated residual keep their registers.
+template <int WM, int WN, int MR, int NR, int PREC, int MRP, bool GATE = false>
 __device__ __forceinline__ void conv16_epilogue(const Conv16Params& p, f32x4_t (&acc)[MR][NR], unsigned char* smem, int wave_d, int wm, int wn,
                                                 int lane, int n0, int y0, int x0, int co0, int NBv, int tile_index, int ph = -1) {
     constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
@@ -137,7 +142,10 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Params& p, f32x4_t (
                 if (p.res) {
                     const float4 rv = *(const float4*)(p.res + ((size_t)(n * (p.H >> p.res_shift) + (oyy >> p.res_shift)) * (p.W >> p.res_shift)
                                                                 + (oxx >> p.res_shift)) * p.Cout + co);
-                    v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+                    if (GATE) {                  // (host-checked: res_shift == 0, Cout % 8 == 0; co % 4 == 0 picks the nibble)
+                        const unsigned m = (unsigned)p.res_bits[(((size_t)(n * p.H + oyy) * p.W + oxx) * p.Cout + co) >> 3] >> (co & 4);
+                        v.x += (m & 1u) ? rv.x : 0.f; v.y += (m & 2u) ? rv.y : 0.f; v.z += (m & 4u) ? rv.z : 0.f; v.w += (m & 8u) ? rv.w : 0.f;
+                    } else { v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w; }
                 }
                 const size_t pix = (size_t)(n * p.H + oyy) * p.W + oxx;
                 if (p.mask16) {
@@ -221,7 +229,7 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Params& p, f32x4_t (
             for (int nr = 0; nr < NR; ++nr) {
                 const int co = co0 + wn * (NR * 16) + nr * 16 + (lane & 15);
                 if (co < p.Cout) {
-                    float v = acc[mr][nr][r] * alpha;      // (element-wise path: channel counts that are no multiple of 4; never split-K)
+                    float v = acc[mr][nr][r] * alpha;      // (element-wise path: channel counts that are no multiple of 4; never split-K, never a gated residual: that needs Cout % 8 == 0)
                     if (p.bias) v += p.bias[co];
                     if (p.res) v += p.res[rpix + co];
                     if (p.mask16 && !((unsigned)(p.mask16[pixi * p.Co8 + co] - 1u) < 0x7fffu)) v = 0.f;

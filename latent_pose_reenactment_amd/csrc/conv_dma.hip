@@ -38,7 +38,7 @@ __device__ __attribute__((aligned(64))) unsigned int lp_zero_page[16];      // w
 // GH (grouped convs with groups of <= 32 channels): output channels [co0, co0 + 32) only contract with the chunk co0 .. co0 + 31 and
 // [co0 + 32, co0 + 64) only with the second chunk -- the other half of every stage's MFMAs multiplies the zeros of the block-diagonal weight
 // image and is skipped (half the matrix work: in the bf16x3 mode the layer-1 / layer-2 grouped convs were bound by it, not by their traffic)
-template <int KS, bool UPS, int WM, int WN, int MR, int NR, int PREC, bool PP, int NBUF = 2, int CC = 32, bool GH = false>
+template <int KS, bool UPS, int WM, int WN, int MR, int NR, int PREC, bool PP, int NBUF = 2, int CC = 32, bool GH = false, bool GATE = false>
 #ifndef LP_PP_MINW
 #define LP_PP_MINW 2          // min waves per SIMD of the ping-pong kernels in the 16-bit modes: 2 = one workgroup per CU, 4 = two (<= 128 VGPRs)
 #endif
@@ -335,7 +335,7 @@ void conv_dma_kernel(Conv16Params p) {
     }
 
     // ---- epilogue (conv_common.h).  1x1 layers transpose 16 rows (one MFMA row block) at a time, 3x3 kernels the whole block
-    conv16_epilogue<WM, WN, MR, NR, PREC, (KS == 1) ? 1 : MR>(p, acc, smem, wave_d, wm, wn, lane, n0, y0, x0, co0, NBv, tile_id, ph);
+    conv16_epilogue<WM, WN, MR, NR, PREC, (KS == 1) ? 1 : MR, GATE>(p, acc, smem, wave_d, wm, wn, lane, n0, y0, x0, co0, NBv, tile_id, ph);
 }
 
 // Split-K finish: y = alpha * sum_s part[s] + bias + res, ReLU mask, 16-bit planes of the consumer -- the whole epilogue of the conv,
@@ -395,9 +395,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(Conv16Params p) {
 // ------------------------------------------------------------------------------------------------------------------
 // host side: tile selection + dispatch
 // ------------------------------------------------------------------------------------------------------------------
-template <int KS, bool UPS, int WM, int WN, int MR, int NR, int PREC, bool PP, int NBUF = 2, int CC = 32, bool GH = false>
+template <int KS, bool UPS, int WM, int WN, int MR, int NR, int PREC, bool PP, int NBUF = 2, int CC = 32, bool GH = false, bool GATE = false>
 static int launch_v(Conv16Params& p, size_t lds, dim3 grid, hipStream_t stream) {
-    auto kern = conv_dma_kernel<KS, UPS, WM, WN, MR, NR, PREC, PP, NBUF, CC, GH>;
+    auto kern = conv_dma_kernel<KS, UPS, WM, WN, MR, NR, PREC, PP, NBUF, CC, GH, GATE>;
     static thread_local int attr_dev = -1;                 // per host thread and device (main and autograd threads both launch)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return lp_set_error(LP_ERR_HIP, "hipGetDevice failed");
@@ -495,8 +495,11 @@ static int launch_conv16(Conv16Params& p, hipStream_t stream) {
         const size_t lds3 = lds_halo + 3 * B_BUF;
         const long long total_wgs = (long long)grid.x * grid.y * grid.z;
         const bool ring = (nbuf_env ? nbuf_env == 3 : total_wgs <= 320) && lds3 <= LDS_MAX;
+        if constexpr (KS == 1) { if (ring && p.res_bits) return launch_v<KS, UPS, WM, WN, MR, NR, PREC, false, 3, CC, GH, true>(p, lds3 > epi ? lds3 : epi, grid, stream); }
         if (ring) return launch_v<KS, UPS, WM, WN, MR, NR, PREC, false, 3, CC, GH>(p, lds3 > epi ? lds3 : epi, grid, stream);
     }
+    // (a gated residual, Conv16Params::res_bits: 1x1 convs only -- their own instantiations, the rest of the family is compiled without the gate)
+    if constexpr (KS == 1) { if (p.res_bits) return launch_v<KS, UPS, WM, WN, MR, NR, PREC, false, 2, CC, GH, true>(p, lds, grid, stream); }
     return launch_v<KS, UPS, WM, WN, MR, NR, PREC, false, 2, CC, GH>(p, lds, grid, stream);
 }
 
@@ -580,13 +583,15 @@ extern "C" int lp_conv16_fwd(const uint16_t* a_hi, const uint16_t* a_lo, const u
 // planes: no fp32 store); (b) stats [rows][Cout][3] | NULL: {count, mean, M2} of the written values per (row block, channel), merged by
 // lp_norm_stats_finalize -- *stats_rows (HOST int, out) = partial rows per image, 0 when this geometry is not covered (small / ragged
 // maps, split-K) and the caller has to run lp_instnorm_stats / lp_bn_train_stats on y instead.
-extern "C" int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo, float* y,
-                                   const float* bias, const float* res, const float* alpha, const float* alpha2,
-                                   int N, int H, int W, int Cin, int Cout, int CinP, int CoutP,
-                                   int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
-                                   uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
-                                   float* stats, long long stats_capacity_floats, int* stats_rows, void* stream) {
+static int conv16_fwd_impl(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo, float* y,
+                          const float* bias, const float* res, const unsigned char* res_bits, const float* alpha, const float* alpha2,
+                          int N, int H, int W, int Cin, int Cout, int CinP, int CoutP,
+                          int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
+                          uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
+                          float* stats, long long stats_capacity_floats, int* stats_rows, void* stream) {
     if (stats_rows) *stats_rows = 0;
+    if (res_bits && (!res || res_shift || (Cout & 7))) return lp_set_error(LP_ERR_ARG, "lp_conv16_fwd_gated: res_bits needs res, res_shift == 0 and Cout % 8 == 0");
+    if (res_bits && (ksize != 1 || upsample)) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_conv16_fwd_gated: res_bits is covered by the 1x1 convs only");
     if (!a_hi || !w_hi) return lp_set_error(LP_ERR_ARG, "lp_conv16_fwd: null pointer");
     if (!y && (!out_hi || (Cout & 7))) return lp_set_error(LP_ERR_ARG, "lp_conv16_fwd: y may only be NULL when out_hi is given and Cout % 8 == 0");
     if (stats && !stats_rows) return lp_set_error(LP_ERR_ARG, "lp_conv16_fwd: stats needs stats_rows");
@@ -597,7 +602,7 @@ extern "C" int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, c
     if (CinP % 32 || CinP < Cin || CoutP % 128 || CoutP < Cout) return lp_set_error(LP_ERR_ARG, "lp_conv16_fwd: bad padded dims");
     if (H < 2 || W < 2) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_conv16_fwd: H,W must be >= 2");
     Conv16Params p;
-    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo; p.y = y; p.bias = bias; p.res = res; p.alpha = alpha; p.alpha2 = alpha2;
+    p.a_hi = a_hi; p.a_lo = a_lo; p.w_hi = w_hi; p.w_lo = w_lo; p.y = y; p.bias = bias; p.res = res; p.res_bits = res_bits; p.alpha = alpha; p.alpha2 = alpha2;
     p.mask16 = relu_mask16; p.o_relu = out_relu; p.part = workspace; p.part_bytes = workspace ? workspace_bytes : 0; p.amax = amax_slots;
     p.o_hi = (Cout & 7) ? nullptr : out_hi; p.o_lo = (Cout & 7) ? nullptr : out_lo;   // (pad channels: the pack pass writes them)
     p.N = N; p.H = H; p.W = W; p.Hin = upsample ? H / 2 : H; p.Win = upsample ? W / 2 : W;
@@ -629,6 +634,31 @@ extern "C" int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, c
     if (out_hi && !p.o_hi)
         return lp_act_pack(y, nullptr, nullptr, (out_relu & 1) ? 2 : 0, out_hi, out_lo, N, H * W, Cout, prec, nullptr, nullptr, 0, 1, nullptr, stream);
     return LP_OK;
+}
+
+extern "C" int lp_conv16_fwd_stats(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo, float* y,
+                                   const float* bias, const float* res, const float* alpha, const float* alpha2,
+                                   int N, int H, int W, int Cin, int Cout, int CinP, int CoutP,
+                                   int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
+                                   uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
+                                   float* stats, long long stats_capacity_floats, int* stats_rows, void* stream) {
+    return conv16_fwd_impl(a_hi, a_lo, w_hi, w_lo, y, bias, res, nullptr, alpha, alpha2, N, H, W, Cin, Cout, CinP, CoutP, ksize, upsample, res_shift, prec,
+                           relu_mask16, out_hi, out_lo, out_relu, workspace, workspace_bytes, amax_slots, stats, stats_capacity_floats, stats_rows, stream);
+}
+
+// lp_conv16_fwd_stats with a GATED residual: res_bits [P][Cout / 8] (one byte per pixel and 8-channel group, bit j = channel 8 g + j; as
+// lp_bn_add_act_bits writes them) | NULL; y += res where the bit is set, += 0 where it is clear -- a select, so a NaN of res under a cleared
+// bit does not reach y.  Needs res, res_shift == 0, Cout % 8 == 0 and ksize == 1 (a 1x1 conv is never split-K: no finish kernel is involved; a 3x3
+// conv with a gated residual is refused, its caller adds a masked fp32 residual as before).  The data gradient of a residual block's first conv adds the skip
+// gradient d_out * [out > 0] this way from d_out itself: no masked fp32 copy of it is written or read.
+extern "C" int lp_conv16_fwd_gated(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo, float* y,
+                                   const float* bias, const float* res, const unsigned char* res_bits, const float* alpha, const float* alpha2,
+                                   int N, int H, int W, int Cin, int Cout, int CinP, int CoutP,
+                                   int ksize, int upsample, int res_shift, int prec, const uint16_t* relu_mask16,
+                                   uint16_t* out_hi, uint16_t* out_lo, int out_relu, float* workspace, long long workspace_bytes, float* amax_slots,
+                                   float* stats, long long stats_capacity_floats, int* stats_rows, void* stream) {
+    return conv16_fwd_impl(a_hi, a_lo, w_hi, w_lo, y, bias, res, res_bits, alpha, alpha2, N, H, W, Cin, Cout, CinP, CoutP, ksize, upsample, res_shift, prec,
+                           relu_mask16, out_hi, out_lo, out_relu, workspace, workspace_bytes, amax_slots, stats, stats_capacity_floats, stats_rows, stream);
 }
 
 // Grouped 3x3 conv (ResNeXt conv2, embedders/unsupervised_pose_separate_embResNeXt_segmentation.py:26 = torchvision resnext50_32x4d:

@@ -428,7 +428,7 @@ int lp_conv1x1_pipe_launch(Conv16Params& p, int prec, hipStream_t s) {
     // contractions.  1: on; 2: every shape (tests).
     const int on = lp_knobs().conv1x1_pipe;
     constexpr int MAXK = 256;
-    if (!on || p.grouped || p.CinP % 32 || p.H < 2 || p.W < 2) return 0;
+    if (!on || p.grouped || p.CinP % 32 || p.H < 2 || p.W < 2 || p.res_bits) return 0;          // (a gated residual: conv_dma_kernel<1>'s GATE forms)
     const long long pix = (long long)p.N * p.H * p.W;
     const int bn = p.Cout <= 64 ? 64 : 128;
     const long long wgs = ((pix + (bn == 64 ? 255 : 127)) / (bn == 64 ? 256 : 128)) * ((p.Cout + bn - 1) / bn);

@@ -7,7 +7,9 @@
 //                  optional 2x2 sum of dA (x2 nearest upsample), fp32 dx (holds g between the passes), optional bf16 (hi + lo) planes
 //   * bn_bwd16_*   (lp_bn_bwd16, lp_bn_bwd16_h): per-channel statistics [C], dx written STRAIGHT to operand planes, g recomputed in pass 3
 // mask_mode 0: the activation's own pattern 0 < x*scale+shift < act_hi (ReLU: act_hi = inf; ReLU6: 6);  1: no mask (a plain norm);
-// 2: mask_src > 0 (the ReLU sits behind a residual add: mask_src = the block output, fp32);  3: the same from a 16-bit operand plane.
+// 2: mask_src > 0 (the ReLU sits behind a residual add: mask_src = the block output, fp32);  3: the same from a 16-bit operand plane;
+// 4: the same from ONE BIT per element (bn_bwd16_* only): mask_src = bytes [P][C / 8], bit j of byte g = channel 8 g + j, as lp_bn_add_act_bits
+// writes them from the HI plane it stores (mode 3's predicate, evaluated once in the forward).
 // X16: x is a 16-BIT-RESIDENT conv output (the unscaled fp16 plane the conv epilogue left instead of fp32 y; C % 8 == 0).
 #include "lp_common.h"
 #include "lp_hip.h"
@@ -32,6 +34,10 @@ __device__ __forceinline__ void norm_mask(float (&g)[W], const float (&xs)[W], c
         const s16xw_t m = *(const s16xw_t*)((const uint16_t*)mask_src + off);
 #pragma unroll
         for (int j = 0; j < W; ++j) g[j] = ((unsigned)((uint16_t)m[j]) - 1u) < 0x7fffu ? g[j] : 0.f;
+    } else if (mask_mode == 4) {            // (off % W == 0 and C % 8 == 0: W = 4 reads the low or the high nibble of its group's byte)
+        const unsigned m = (unsigned)((const unsigned char*)mask_src)[off >> 3] >> (W == 4 ? (unsigned)(off & 4) : 0u);
+#pragma unroll
+        for (int j = 0; j < W; ++j) g[j] = ((m >> j) & 1u) ? g[j] : 0.f;
     } else if (mask_mode == 0) {
 #pragma unroll
         for (int j = 0; j < W; ++j) { const float t = fmaf(xs[j], a[j], b[j]); g[j] = (t > 0.f && t < act_hi) ? g[j] : 0.f; }
@@ -272,6 +278,22 @@ extern "C" int lp_adain_relu_bwd16(const float* dA, const uint16_t* x16, const f
 // 8 B read in pass 1 and 8 B read + 2 B written in pass 3 per element (fp16 mode), against 30 B for partial + apply + lp_act_pack on fp32 dy.
 // X16: 6 B read per element and pass instead of 8 B.
 // ------------------------------------------------------------------------------------------------------------------
+// block reduction of pass 1: the 16 pixel lanes of each of the block's 64 channels -> part[s][c] = {S1, S2, max|g|, max|xhat|}.  Ends with no
+// barrier: a second call in the same kernel needs one before it
+__device__ __forceinline__ void bn_bwd16_partial_store(float (&sh)[4][16][64], const float (&s1)[4], const float (&s2)[4], const float (&gm)[4],
+                                                       const float (&xm)[4], float* __restrict__ part, int s, int cb, int C) {
+    const int cq = threadIdx.x & 15, pl = threadIdx.x >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { sh[0][pl][cq * 4 + j] = s1[j]; sh[1][pl][cq * 4 + j] = s2[j]; sh[2][pl][cq * 4 + j] = gm[j]; sh[3][pl][cq * 4 + j] = xm[j]; }
+    __syncthreads();
+    const int which = threadIdx.x >> 6, ch = threadIdx.x & 63;
+    float a = 0.f;
+    if (which < 2) { for (int k = 0; k < 16; ++k) a += sh[which][k][ch]; }
+    else { for (int k = 0; k < 16; ++k) a = fmaxf(a, sh[which][k][ch]); }
+    const int cg = cb * 64 + ch;
+    if (cg < C) part[((size_t)s * C + cg) * 4 + which] = a;
+}
+
 template <bool X16>
 __global__ __launch_bounds__(256) void bn_bwd16_partial_kernel(const float* __restrict__ dA, const void* __restrict__ x, const void* __restrict__ mask_src,
                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -301,17 +323,47 @@ __global__ __launch_bounds__(256) void bn_bwd16_partial_kernel(const float* __re
             }
         }
     }
+    bn_bwd16_partial_store(sh, s1, s2, gm, xm, part, s, cb, C);
+}
+
+// DUAL form of pass 1: two BatchNorms (a, b) that receive the SAME masked gradient g = dA * mask -- bn3 and the downsample BatchNorm of a
+// residual block's first bottleneck.  dA and the mask are read once, each BN's x once; per BN the partials, the per-thread accumulation order and
+// the block reduction are those of the single form, so everything downstream is bit-identical to two separate calls.  Mask modes 1 .. 4 (a
+// pattern that does not depend on x).
+template <bool X16>
+__global__ __launch_bounds__(256) void bn_bwd16_partial2_kernel(const float* __restrict__ dA, const void* __restrict__ xa, const void* __restrict__ xb,
+                                                                const void* __restrict__ mask_src, const float* __restrict__ mean_a,
+                                                                const float* __restrict__ rstd_a, const float* __restrict__ mean_b,
+                                                                const float* __restrict__ rstd_b, float* __restrict__ part_a, float* __restrict__ part_b,
+                                                                long long P, int C, int mask_mode, int PB) {
+    __shared__ float sh[4][16][64];
+    const int cb = blockIdx.y, s = blockIdx.x;
+    const int cq = threadIdx.x & 15, pl = threadIdx.x >> 4;
+    const int c = cb * 64 + cq * 4;
+    const long long p0 = (long long)s * PB, p1 = min(P, p0 + PB);
+    float s1[4] = {0, 0, 0, 0}, gm[4] = {0, 0, 0, 0};
+    float s2a[4] = {0, 0, 0, 0}, xma[4] = {0, 0, 0, 0}, s2b[4] = {0, 0, 0, 0}, xmb[4] = {0, 0, 0, 0};
+    if (c < C) {
+        const float4 mua = *(const float4*)(mean_a + c), rsa = *(const float4*)(rstd_a + c), mub = *(const float4*)(mean_b + c), rsb = *(const float4*)(rstd_b + c);
+        const float ma[4] = {mua.x, mua.y, mua.z, mua.w}, ra[4] = {rsa.x, rsa.y, rsa.z, rsa.w}, mb[4] = {mub.x, mub.y, mub.z, mub.w}, rb[4] = {rsb.x, rsb.y, rsb.z, rsb.w};
+#pragma unroll 4
+        for (long long pix = p0 + pl; pix < p1; pix += 16) {
+            const float4 gv = *(const float4*)(dA + pix * C + c), xva = lp_ldx4<X16>(xa, pix * C + c), xvb = lp_ldx4<X16>(xb, pix * C + c);
+            float g[4] = {gv.x, gv.y, gv.z, gv.w};
+            const float xsa[4] = {xva.x, xva.y, xva.z, xva.w}, xsb[4] = {xvb.x, xvb.y, xvb.z, xvb.w};
+            norm_mask<4>(g, xsa, ma, ma, mask_mode, 0.f, mask_src, pix * C + c);      // (modes 1 .. 4: x, scale and shift are not looked at)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { sh[0][pl][cq * 4 + j] = s1[j]; sh[1][pl][cq * 4 + j] = s2[j]; sh[2][pl][cq * 4 + j] = gm[j]; sh[3][pl][cq * 4 + j] = xm[j]; }
-    __syncthreads();
-    {
-        const int which = threadIdx.x >> 6, ch = threadIdx.x & 63;
-        float a = 0.f;
-        if (which < 2) { for (int k = 0; k < 16; ++k) a += sh[which][k][ch]; }
-        else { for (int k = 0; k < 16; ++k) a = fmaxf(a, sh[which][k][ch]); }
-        const int cg = cb * 64 + ch;
-        if (cg < C) part[((size_t)s * C + cg) * 4 + which] = a;
+            for (int j = 0; j < 4; ++j) {
+                const float xha = (xsa[j] - ma[j]) * ra[j], xhb = (xsb[j] - mb[j]) * rb[j];
+                s1[j] += g[j]; gm[j] = fmaxf(gm[j], fabsf(g[j]));
+                s2a[j] = fmaf(g[j], xha, s2a[j]); xma[j] = fmaxf(xma[j], fabsf(xha));
+                s2b[j] = fmaf(g[j], xhb, s2b[j]); xmb[j] = fmaxf(xmb[j], fabsf(xhb));
+            }
+        }
     }
+    bn_bwd16_partial_store(sh, s1, s2a, gm, xma, part_a, s, cb, C);
+    __syncthreads();
+    bn_bwd16_partial_store(sh, s1, s2b, gm, xmb, part_b, s, cb, C);
 }
 
 // one wave per channel: merges the S partials; coef[c] = {ca, cb, cc}, bound[c] >= max|dy| of the channel
@@ -413,6 +465,65 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_rows_kernel(const float* _
         bn_bwd16_apply_item<PREC, X16>(dA, x, mask_src, a8, b8, cf, 1.f, hi, lo, g_out, (size_t)pix * C + c, mask_mode, act_hi);
 }
 
+// DUAL form of pass 3 (see bn_bwd16_partial2_kernel): g from dA and the mask once, then dy of BN a and of BN b from its own x and coefficients
+template <int PREC, bool X16>
+__device__ __forceinline__ void bn_bwd16_apply_item2(const float* dA, const void* xa, const void* xb, const void* mask_src, const float* cfa,
+                                                     const float* cfb, float post_a, float post_b, uint16_t* hi_a, uint16_t* lo_a, uint16_t* hi_b,
+                                                     uint16_t* lo_b, size_t off, int mask_mode) {
+    constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
+    const float4 g0 = *(const float4*)(dA + off), g1 = *(const float4*)(dA + off + 4);
+    float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, xs[8], v[8];
+    load8<X16>(xa, off, xs);
+    norm_mask<8>(g, xs, cfa, cfa, mask_mode, 0.f, mask_src, off);      // (modes 1 .. 4: x, scale and shift are not looked at)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = fmaf(cfa[j * 3], g[j], fmaf(cfa[j * 3 + 1], xs[j], cfa[j * 3 + 2])) * post_a;
+    store_op8<F16, SPLIT>(v, hi_a, lo_a, off);
+    load8<X16>(xb, off, xs);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = fmaf(cfb[j * 3], g[j], fmaf(cfb[j * 3 + 1], xs[j], cfb[j * 3 + 2])) * post_b;
+    store_op8<F16, SPLIT>(v, hi_b, lo_b, off);
+}
+
+struct BnBwd16Dual {          // what pass 3 needs of one of the two BatchNorms
+    const void* x; const float* coef; const float* bound; uint16_t* hi; uint16_t* lo; float* out_scale;
+};
+
+template <int PREC, bool X16>
+__global__ __launch_bounds__(256) void bn_bwd16_apply2_kernel(const float* __restrict__ dA, const void* __restrict__ mask_src, BnBwd16Dual a, BnBwd16Dual b,
+                                                              long long items, int C, int mask_mode) {
+    const float sa = bn_bwd16_out_scale<PREC == LP_PREC_F16>(a.bound, C, a.out_scale);
+    __syncthreads();                                                          // (the scale prologue's shared scratch is used again)
+    const float sb = bn_bwd16_out_scale<PREC == LP_PREC_F16>(b.bound, C, b.out_scale);
+    const int G = C >> 3;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % G) * 8;
+        bn_bwd16_apply_item2<PREC, X16>(dA, a.x, b.x, mask_src, a.coef + c * 3, b.coef + c * 3, sa, sb, a.hi, a.lo, b.hi, b.lo, (size_t)i * 8, mask_mode);
+    }
+}
+
+template <int PREC, bool X16>
+__global__ __launch_bounds__(256) void bn_bwd16_apply2_rows_kernel(const float* __restrict__ dA, const void* __restrict__ mask_src, BnBwd16Dual a, BnBwd16Dual b,
+                                                                   long long P, int C, int rows, int PB, int mask_mode) {
+    const float sa = bn_bwd16_out_scale<PREC == LP_PREC_F16>(a.bound, C, a.out_scale);
+    __syncthreads();
+    const float sb = bn_bwd16_out_scale<PREC == LP_PREC_F16>(b.bound, C, b.out_scale);
+    const int G = C >> 3;
+    const int cg = threadIdx.x % G, r = threadIdx.x / G;
+    if (r >= rows) return;
+    const int c = cg * 8;
+    float cfa[24], cfb[24];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const float4 q = *(const float4*)(a.coef + (size_t)c * 3 + j * 4), t = *(const float4*)(b.coef + (size_t)c * 3 + j * 4);
+        cfa[j * 4] = q.x * sa; cfa[j * 4 + 1] = q.y * sa; cfa[j * 4 + 2] = q.z * sa; cfa[j * 4 + 3] = q.w * sa;      // power of two: exact
+        cfb[j * 4] = t.x * sb; cfb[j * 4 + 1] = t.y * sb; cfb[j * 4 + 2] = t.z * sb; cfb[j * 4 + 3] = t.w * sb;
+    }
+    const long long p0 = (long long)blockIdx.x * PB, p1 = min(P, p0 + PB);
+#pragma unroll 2
+    for (long long pix = p0 + r; pix < p1; pix += rows)
+        bn_bwd16_apply_item2<PREC, X16>(dA, a.x, b.x, mask_src, cfa, cfb, 1.f, 1.f, a.hi, a.lo, b.hi, b.lo, (size_t)pix * C + c, mask_mode);
+}
+
 extern "C" long long lp_bn_bwd16_workspace_bytes(long long P, int C) {
     const int PB = lp_stat_split_pix(1, P, C);
     const long long S = (P + PB - 1) / PB;
@@ -464,7 +575,7 @@ static int bn_bwd16_impl(const BnBwd16Params& p) {
     if (!p.dA || !p.x || !p.gamma || !p.mean || !p.rstd || !p.scale || !p.shift || !p.out_hi || !p.out_scale || !p.dgamma || !p.dbeta || !p.workspace)
         return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: null pointer");
     if (p.C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16: C must be a multiple of 8");
-    if (p.mask_mode < 0 || p.mask_mode > 3 || (p.mask_mode >= 2 && !p.mask_src)) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: bad mask mode");
+    if (p.mask_mode < 0 || p.mask_mode > 4 || (p.mask_mode >= 2 && !p.mask_src)) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: bad mask mode");
     if (p.prec == LP_PREC_BF16X3 && !p.out_lo) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: bf16x3 needs the lo plane");
     if (p.x16 && p.prec != LP_PREC_F16) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16_h: 16-bit x exists in the fp16 mode only");
     if (p.P < 1) return LP_OK;
@@ -477,7 +588,8 @@ static int bn_bwd16_impl(const BnBwd16Params& p) {
 
 // x as fp32 (x16 = NULL) or as the fp16 plane a conv epilogue wrote instead of fp32 y (x = NULL, fp16 mode); mask modes 0 / 1 / 2 as
 // lp_bn_bwd16 (2: mask_src fp32 > 0) and 3: mask_src = a 16-bit OPERAND PLANE [P][C] whose elements are > 0 (the block output's planes:
-// 2 B instead of 4 B per element for the ReLU pattern behind the residual add)
+// 2 B instead of 4 B per element for the ReLU pattern behind the residual add) and 4: mask_src = the same pattern as one bit per element
+// (bytes [P][C / 8] from lp_bn_add_act_bits)
 extern "C" int lp_bn_bwd16_h(const float* dA, const float* x, const uint16_t* x16, const void* mask_src, const float* gamma, const float* mean,
                              const float* rstd, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo, float* out_scale,
                              float* dgamma, float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats,
@@ -496,7 +608,76 @@ extern "C" int lp_bn_bwd16(const float* dA, const float* x, const float* mask_sr
                            float* dbeta, float* workspace, long long P, int C, int mask_mode, float act_hi, int frozen_stats, int prec,
                            float* g_out, void* stream) {
     if (!x) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: null pointer");
-    if (mask_mode == 3) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: mask mode 3 (16-bit plane) is lp_bn_bwd16_h's");
+    if (mask_mode >= 3) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16: mask modes 3 (16-bit plane) and 4 (bit pattern) are lp_bn_bwd16_h's");
     return lp_bn_bwd16_h(dA, x, nullptr, mask_src, gamma, mean, rstd, scale, shift, out_hi, out_lo, out_scale, dgamma, dbeta, workspace, P, C,
                          mask_mode, act_hi, frozen_stats, prec, g_out, stream);
+}
+
+// the passes of the dual form for one instantiation: two partial sets, two finalize launches (the single form's kernel), one apply
+template <int PREC, bool X16> static int bn_bwd16_dual_launch(const float* dA, const void* mask_src, const BnBwd16Params& a, const BnBwd16Params& b) {
+    const long long P = a.P;
+    const int C = a.C, G = C >> 3;
+    const int PB = lp_stat_split_pix(1, P, C);
+    const int S = (int)((P + PB - 1) / PB);
+    float* part[2] = {a.workspace, b.workspace};
+    float* coef[2] = {a.workspace + (size_t)S * C * 4, b.workspace + (size_t)S * C * 4};
+    float* bound[2] = {coef[0] + (size_t)C * 3, coef[1] + (size_t)C * 3};
+    hipLaunchKernelGGL(bn_bwd16_partial2_kernel<X16>, dim3(S, (C + 63) / 64), dim3(256), 0, a.stream, dA, a.x, b.x, mask_src, a.mean, a.rstd, b.mean, b.rstd,
+                       part[0], part[1], P, C, a.mask_mode, PB);
+    int rc = lp_check_launch("bn_bwd16_partial2");
+    if (rc) return rc;
+    const BnBwd16Params* q[2] = {&a, &b};
+    for (int k = 0; k < 2; ++k) {
+        hipLaunchKernelGGL(bn_bwd16_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, a.stream, part[k], q[k]->gamma, q[k]->mean, q[k]->rstd, q[k]->dgamma,
+                           q[k]->dbeta, coef[k], bound[k], C, S, 1.0f / (float)P, a.frozen_stats);
+        rc = lp_check_launch("bn_bwd16_finalize");
+        if (rc) return rc;
+    }
+    const BnBwd16Dual da = {a.x, coef[0], bound[0], a.out_hi, a.out_lo, a.out_scale}, db = {b.x, coef[1], bound[1], b.out_hi, b.out_lo, b.out_scale};
+    if (G <= 256) {          // (the grid rule of bn_bwd16_launch)
+        const int rows = 256 / G;
+        long long ppb = (P + 4095) / 4096;
+        if (ppb < 4ll * rows) ppb = 4ll * rows;
+        ppb = (ppb + rows - 1) / rows * rows;
+        hipLaunchKernelGGL((bn_bwd16_apply2_rows_kernel<PREC, X16>), dim3((unsigned)((P + ppb - 1) / ppb)), dim3(256), 0, a.stream, dA, mask_src, da, db, P, C,
+                           rows, (int)ppb, a.mask_mode);
+    } else {
+        const long long items = P * G, blocks = (items + 255) / 256;
+        hipLaunchKernelGGL((bn_bwd16_apply2_kernel<PREC, X16>), dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, a.stream, dA, mask_src, da, db,
+                           items, C, a.mask_mode);
+    }
+    return lp_check_launch("bn_bwd16_apply2");
+}
+
+// Two BatchNorm backwards over the SAME incoming gradient and ReLU pattern in one pass pair: out = relu(BN_a(xa) + BN_b(xb)) (bn3 and the
+// downsample BatchNorm of a residual block).  Per BN the arguments and results of lp_bn_bwd16_h (each with its own workspace of
+// lp_bn_bwd16_workspace_bytes), bit-identical to two lp_bn_bwd16_h calls; dA and the pattern are read once per pass instead of twice.
+// xa / xb: both fp32 (xa16 = xb16 = NULL) or both fp16 planes (xa = xb = NULL, fp16 mode).  mask_mode 1 .. 4 (a pattern that does not depend on x).
+extern "C" int lp_bn_bwd16_dual(const float* dA, const void* mask_src, const float* xa, const uint16_t* xa16, const float* gamma_a, const float* mean_a,
+                                const float* rstd_a, uint16_t* hi_a, uint16_t* lo_a, float* out_scale_a, float* dgamma_a, float* dbeta_a,
+                                float* workspace_a, const float* xb, const uint16_t* xb16, const float* gamma_b, const float* mean_b,
+                                const float* rstd_b, uint16_t* hi_b, uint16_t* lo_b, float* out_scale_b, float* dgamma_b, float* dbeta_b,
+                                float* workspace_b, long long P, int C, int mask_mode, int frozen_stats, int prec, void* stream) {
+    if ((xa16 != nullptr) != (xb16 != nullptr)) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16_dual: both x as fp32 or both as fp16 planes");
+    const bool x16 = xa16 != nullptr;
+    BnBwd16Params a, b;
+    a.dA = dA; a.x = x16 ? (const void*)xa16 : (const void*)xa; a.x16 = x16; a.mask_src = mask_src; a.gamma = gamma_a; a.mean = mean_a; a.rstd = rstd_a;
+    a.scale = a.shift = nullptr; a.out_hi = hi_a; a.out_lo = lo_a; a.out_scale = out_scale_a; a.dgamma = dgamma_a; a.dbeta = dbeta_a; a.workspace = workspace_a;
+    a.P = P; a.C = C; a.mask_mode = mask_mode; a.act_hi = 0.f; a.frozen_stats = frozen_stats; a.prec = prec; a.g_out = nullptr; a.stream = (hipStream_t)stream;
+    b = a;
+    b.x = x16 ? (const void*)xb16 : (const void*)xb; b.gamma = gamma_b; b.mean = mean_b; b.rstd = rstd_b; b.out_hi = hi_b; b.out_lo = lo_b;
+    b.out_scale = out_scale_b; b.dgamma = dgamma_b; b.dbeta = dbeta_b; b.workspace = workspace_b;
+    for (const BnBwd16Params* q : {&a, &b})
+        if (!dA || !q->x || !q->gamma || !q->mean || !q->rstd || !q->out_hi || !q->out_scale || !q->dgamma || !q->dbeta || !q->workspace)
+            return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16_dual: null pointer");
+    if (C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16_dual: C must be a multiple of 8");
+    if (mask_mode < 1 || mask_mode > 4 || (mask_mode >= 2 && !mask_src)) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16_dual: mask mode 1 .. 4");
+    if (prec == LP_PREC_BF16X3 && (!lo_a || !lo_b)) return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16_dual: bf16x3 needs the lo planes");
+    if (x16 && prec != LP_PREC_F16) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_bwd16_dual: 16-bit x exists in the fp16 mode only");
+    if (P < 1) return LP_OK;
+    if (x16) return bn_bwd16_dual_launch<LP_PREC_F16, true>(dA, mask_src, a, b);
+    if (prec == LP_PREC_BF16) return bn_bwd16_dual_launch<LP_PREC_BF16, false>(dA, mask_src, a, b);
+    if (prec == LP_PREC_BF16X3) return bn_bwd16_dual_launch<LP_PREC_BF16X3, false>(dA, mask_src, a, b);
+    if (prec == LP_PREC_F16) return bn_bwd16_dual_launch<LP_PREC_F16, false>(dA, mask_src, a, b);
+    return lp_set_error(LP_ERR_ARG, "lp_bn_bwd16_dual: unknown precision mode");
 }

@@ -190,7 +190,8 @@ __global__ __launch_bounds__(256) void bn_add_act_kernel(const void* __restrict_
                                                          const float* __restrict__ res, const float* __restrict__ rsc, const float* __restrict__ rsh,
                                                          float* __restrict__ out, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
                                                          long long items, int C, int relu,
-                                                         const uint16_t* __restrict__ rhi = nullptr, const uint16_t* __restrict__ rlo = nullptr) {
+                                                         const uint16_t* __restrict__ rhi = nullptr, const uint16_t* __restrict__ rlo = nullptr,
+                                                         unsigned char* __restrict__ bits = nullptr) {
     constexpr bool SPLIT = (PREC == LP_PREC_BF16X3), F16 = (PREC == LP_PREC_F16);
     const int G = C >> 3;
     const float floor_v = relu ? 0.f : -3.0e38f;
@@ -227,19 +228,27 @@ __global__ __launch_bounds__(256) void bn_add_act_kernel(const void* __restrict_
             *(float4*)(out + i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
         if (hi) store_op8<F16, SPLIT>(v, hi, lo, (size_t)i * 8);
+        if (bits) {       // bit j: the HI word this thread stores for channel c + j is > 0 (sign clear, magnitude non-zero) -- the predicate of norm_mask mode 3
+            unsigned b = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) b |= (((unsigned)lp_f32_to_op16<F16>(v[j]) - 1u) < 0x7fffu) ? (1u << j) : 0u;
+            bits[i] = (unsigned char)b;
+        }
     }
 }
 
 static int bn_add_act_impl(const float* y, const uint16_t* y16, const float* scale, const float* shift, const float* res, const float* res_scale,
-                           const float* res_shift, float* out, uint16_t* hi, uint16_t* lo, long long P, int C, int relu, int prec, hipStream_t st) {
+                           const float* res_shift, float* out, uint16_t* hi, uint16_t* lo, unsigned char* bits, long long P, int C, int relu, int prec,
+                           hipStream_t st) {
     if ((!y && !y16) || !scale || !shift || (!out && !hi)) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act: null pointer");      // (out NULL: planes only, ABI 12)
     if (!res_scale != !res_shift || (res_scale && !res)) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act: res_scale/res_shift go together and need res");
     if (C & 7) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_add_act: C must be a multiple of 8");
     if (hi && prec == LP_PREC_BF16X3 && !lo) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act: bf16x3 planes need lo");
     if (y16 && prec != LP_PREC_F16) return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_add_act16: 16-bit y exists in the fp16 mode only");
+    if (bits && !hi) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act_bits: the bit pattern is the one of the HI plane, which must be written");
     const long long items = P * (C >> 3);
     if (items == 0) return LP_OK;
-#define LP_BA(Q, H, SRC) hipLaunchKernelGGL((bn_add_act_kernel<Q, H>), dim3(grid_for(items)), dim3(256), 0, st, (const void*)(SRC), scale, shift, res, res_scale, res_shift, out, hi, lo, items, C, relu)
+#define LP_BA(Q, H, SRC) hipLaunchKernelGGL((bn_add_act_kernel<Q, H>), dim3(grid_for(items)), dim3(256), 0, st, (const void*)(SRC), scale, shift, res, res_scale, res_shift, out, hi, lo, items, C, relu, nullptr, nullptr, bits)
     if (y16) LP_BA(LP_PREC_F16, true, y16);
     else if (prec == LP_PREC_BF16) LP_BA(LP_PREC_BF16, false, y);
     else if (prec == LP_PREC_BF16X3) LP_BA(LP_PREC_BF16X3, false, y);
@@ -252,13 +261,29 @@ static int bn_add_act_impl(const float* y, const uint16_t* y16, const float* sca
 extern "C" int lp_bn_add_act(const float* y, const float* scale, const float* shift, const float* res, const float* res_scale,
                              const float* res_shift, float* out, uint16_t* hi, uint16_t* lo, long long P, int C, int relu, int prec,
                              void* stream) {
+    return lp_bn_add_act_bits(y, scale, shift, res, res_scale, res_shift, out, hi, lo, nullptr, P, C, relu, prec, stream);
+}
+
+// lp_bn_add_act that also leaves the ReLU pattern of the block output as ONE BIT per element: bits [P][C / 8] (| NULL), one byte per pixel and
+// 8-channel group, bit j = channel 8 g + j, set where the stored HI plane word is > 0 (needs hi).  What the backward's mask mode 4 and
+// lp_conv16_fwd_gated read instead of the 16-bit plane / a masked fp32 gradient.
+extern "C" int lp_bn_add_act_bits(const float* y, const float* scale, const float* shift, const float* res, const float* res_scale,
+                                  const float* res_shift, float* out, uint16_t* hi, uint16_t* lo, unsigned char* bits, long long P, int C, int relu,
+                                  int prec, void* stream) {
     if (!y) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act: null pointer");
-    return bn_add_act_impl(y, nullptr, scale, shift, res, res_scale, res_shift, out, hi, lo, P, C, relu, prec, (hipStream_t)stream);
+    return bn_add_act_impl(y, nullptr, scale, shift, res, res_scale, res_shift, out, hi, lo, bits, P, C, relu, prec, (hipStream_t)stream);
 }
 
 // identity bottleneck of a bf16 / bf16x3 network: the residual from the operand planes of the block input, fp32 ``out`` optional (ABI 12)
 extern "C" int lp_bn_add_act_planes(const float* y, const float* scale, const float* shift, const uint16_t* res_hi, const uint16_t* res_lo,
                                     float* out, uint16_t* hi, uint16_t* lo, long long P, int C, int relu, int prec, void* stream) {
+    return lp_bn_add_act_planes_bits(y, scale, shift, res_hi, res_lo, out, hi, lo, nullptr, P, C, relu, prec, stream);
+}
+
+// lp_bn_add_act_planes + the one-bit ReLU pattern (as lp_bn_add_act_bits)
+extern "C" int lp_bn_add_act_planes_bits(const float* y, const float* scale, const float* shift, const uint16_t* res_hi, const uint16_t* res_lo,
+                                         float* out, uint16_t* hi, uint16_t* lo, unsigned char* bits, long long P, int C, int relu, int prec,
+                                         void* stream) {
     if (!y || !scale || !shift || !res_hi || !hi) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act_planes: null pointer");
     if (prec != LP_PREC_BF16 && prec != LP_PREC_BF16X3)
         return lp_set_error(LP_ERR_UNSUPPORTED, "lp_bn_add_act_planes: bf16 / bf16x3 planes only (an fp16 plane has 11 bits: not a residual stream)");
@@ -269,18 +294,25 @@ extern "C" int lp_bn_add_act_planes(const float* y, const float* scale, const fl
     const float* nof = nullptr;
     if (prec == LP_PREC_BF16X3)
         hipLaunchKernelGGL((bn_add_act_kernel<LP_PREC_BF16X3, false, true>), dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, (const void*)y, scale, shift,
-                           nof, nof, nof, out, hi, lo, items, C, relu, res_hi, res_lo);
+                           nof, nof, nof, out, hi, lo, items, C, relu, res_hi, res_lo, bits);
     else
         hipLaunchKernelGGL((bn_add_act_kernel<LP_PREC_BF16, false, true>), dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, (const void*)y, scale, shift,
-                           nof, nof, nof, out, hi, lo, items, C, relu, res_hi, res_lo);
+                           nof, nof, nof, out, hi, lo, items, C, relu, res_hi, res_lo, bits);
     return lp_check_launch("bn_add_act_planes");
 }
 
 // y as the fp16 plane a conv epilogue wrote instead of fp32 (fp16 mode)
 extern "C" int lp_bn_add_act16(const uint16_t* y16, const float* scale, const float* shift, const float* res, const float* res_scale,
                                const float* res_shift, float* out, uint16_t* hi, long long P, int C, int relu, void* stream) {
+    return lp_bn_add_act16_bits(y16, scale, shift, res, res_scale, res_shift, out, hi, nullptr, P, C, relu, stream);
+}
+
+// lp_bn_add_act16 + the one-bit ReLU pattern (as lp_bn_add_act_bits)
+extern "C" int lp_bn_add_act16_bits(const uint16_t* y16, const float* scale, const float* shift, const float* res, const float* res_scale,
+                                    const float* res_shift, float* out, uint16_t* hi, unsigned char* bits, long long P, int C, int relu,
+                                    void* stream) {
     if (!y16) return lp_set_error(LP_ERR_ARG, "lp_bn_add_act16: null pointer");
-    return bn_add_act_impl(nullptr, y16, scale, shift, res, res_scale, res_shift, out, hi, nullptr, P, C, relu, LP_PREC_F16, (hipStream_t)stream);
+    return bn_add_act_impl(nullptr, y16, scale, shift, res, res_scale, res_shift, out, hi, nullptr, bits, P, C, relu, LP_PREC_F16, (hipStream_t)stream);
 }
 
 // ---- BatchNorm affine (+ ReLU) of a 16-bit-resident conv output, to the operand planes of the next conv (fp16 mode) ----------------

@@ -48,6 +48,12 @@ def supported(n: int, h: int, w: int) -> bool:
 Y16 = os.environ.get('LP_E_Y16', '1') != '0'        # fp16 mode: conv outputs stay 16-bit resident
 RES16 = os.environ.get('LP_E_RES16', '1') != '0'    # identity shortcuts of bf16x3 blocks read the block input from its operand planes (hi + lo); no fp32 block output there
 MASK16 = os.environ.get('LP_E_MASK16', '1') != '0'  # block-output ReLU pattern from the operand planes in every mode (0: from the fp32 copy outside the fp16 mode)
+MASKBITS = os.environ.get('LP_E_MASKBITS', '1') != '0'  # (with MASK16) that pattern as ONE BIT per element, written by the block-output kernel: the junction backward reads 1/8 B instead of 2 B per element and BatchNorm, identity blocks add the skip gradient gated by the bits (no fp32 masked copy of d_out), downsample blocks run bn3 and the downsample BatchNorm as one pass pair (0: the plane route)
+
+
+def _maskbits():
+    """the bit-pattern route is on (the fp64 emulation the CPU tests put in place of ``ops`` restates the plane route only: same values)"""
+    return MASKBITS and MASK16 and hasattr(ops, 'bn_bwd16_dual')
 
 
 def _side_ok(t):
@@ -59,13 +65,15 @@ def _v16(a, shape):
     return ops.Act16(a.hi.view(shape), None if a.lo is None else a.lo.view(shape), a.c, a.inv)
 
 
-def _conv1x1(a16, pack, prec, bias=None, res=None, amax=False, stats=False, y16=False):
+def _conv1x1(a16, pack, prec, bias=None, res=None, amax=False, stats=False, y16=False, res_bits=None):
     """1x1 contraction on flattened pixels: a16 [..., C8] planes -> y [P, Cout] fp32 (``stats``: -> (y, ConvStats | None): the BatchNorm
     partials of y over all P pixels, written by the conv epilogue).  ``y16``: y is returned as its fp16 plane (``Act16``), no fp32 y."""
     fa = ops.flat16(a16)
     _, h, w, _ = fa.hi.shape
     if res is not None:
         res = res.view(1, h, w, -1)
+    if res_bits is not None:          # gated residual (the skip gradient of an identity block): res where the bit is set
+        return ops.conv16(fa, pack, ksize=1, bias=bias, res=res, res_bits=res_bits.view(1, h, w, -1), prec=prec, amax=amax, kind='conv1x1')
     if y16:
         out = ops.conv16(fa, pack, ksize=1, bias=bias, res=res, prec=prec, stats=stats, want_y=False, out16=0, kind='conv1x1')
         return out[1:] if stats else out[1]
@@ -134,6 +142,7 @@ class ResNeXtFunction(torch.autograd.Function):
         lprecs = net.layer_precs()          # mode per contraction (the block's mode unless LP_E_HEAD_F16 moves a layer kind of the head to fp16)
         out, out16, idx = ops.bn_relu_maxpool(y0, st0.scale, st0.shift, lprecs[(net._hip_blocks[0][0], 'conv1')], want_idx=need_grad)
         saved_blocks = []
+        bkw = {'want_bits': True} if (need_grad and _maskbits()) else {}          # the block outputs' one-bit ReLU pattern for the backward
         # ---- bottleneck blocks.  Inside the loop ``prec`` is the block's own mode; the block output's operand planes are written in the
         # mode of the block that consumes them.
         base_prec = prec
@@ -178,18 +187,19 @@ class ResNeXtFunction(torch.autograd.Function):
                 yd = yd.view(n, ho, wo, cout)
                 std = bn(yd, bname + '.downsample.1', cs)
                 need_f32 = bi + 1 >= nblk or not (net._hip_blocks[bi + 1][5] or planes_res[bi + 1])          # (as below: who reads an fp32 block output)
-                out, out16 = ops.bn_add_act(y3, st3.scale, st3.shift, yd, std.scale, std.shift, relu=True, prec=nprec, want_out=need_f32 or not MASK16)
+                out, out16, *bits = ops.bn_add_act(y3, st3.scale, st3.shift, yd, std.scale, std.shift, relu=True, prec=nprec, want_out=need_f32 or not MASK16, **bkw)
             elif planes_res[bi]:
                 # identity shortcut from the operand planes of the block input (hi + lo: the values conv1 multiplied); the fp32 copy of the block
                 # output is only written when something reads it: an identity block that takes the fp32 route, or the pooling head behind the last block
                 need_f32 = bi + 1 >= nblk or not (net._hip_blocks[bi + 1][5] or planes_res[bi + 1])
-                out, out16 = ops.bn_add_act(y3, st3.scale, st3.shift, xin16, relu=True, prec=nprec, want_out=need_f32)
+                out, out16, *bits = ops.bn_add_act(y3, st3.scale, st3.shift, xin16, relu=True, prec=nprec, want_out=need_f32, **bkw)
             else:
-                out, out16 = ops.bn_add_act(y3, st3.scale, st3.shift, xin, relu=True, prec=nprec)
+                out, out16, *bits = ops.bn_add_act(y3, st3.scale, st3.shift, xin, relu=True, prec=nprec, **bkw)
             if need_grad:
                 # (the ReLU pattern of the block output is read from the HI plane of its operand planes -- 2 B per element in every mode (round 6; the
                 #  16-bit-resident mode did so since round 3): relu(out) > 0 <=> its bf16 / fp16 rounding > 0, and the fp32 copy is not kept alive)
-                saved_blocks.append((xin16, y1, st1, a1, y2, st2, a2, y3, st3, xd16, yd, std, out16 if MASK16 else (out16 if y16 else out), (h, w, ho, wo), (p1, p2, p3)))
+                saved_blocks.append((xin16, y1, st1, a1, y2, st2, a2, y3, st3, xd16, yd, std, out16 if MASK16 else (out16 if y16 else out), (h, w, ho, wo), (p1, p2, p3),
+                                     bits[0] if bits else None))
         # ---- head
         prec = base_prec
         _, hl, wl, cl = out.shape
@@ -249,9 +259,20 @@ class ResNeXtFunction(torch.autograd.Function):
         d_out = ops.spatial_mean_bwd(d_pooled, hl, wl)                            # [N, hl, wl, 2048]
         # ---- blocks, last to first
         for (bname, cin, width, cout, stride, down), sv in zip(reversed(net._hip_blocks), reversed(ctx.blocks)):
-            xin16, y1, st1, a1, y2, st2, a2, y3, st3, xd16, yd, std, out, (h, w, ho, wo), (p1, p2, p3) = sv       # operand modes of conv1 (+ downsample), conv2, conv3
-            # out = relu(bn3(y3) + skip): g = d_out * [out > 0] reaches bn3 and the skip branch alike
-            d16, g = bn_bwd(d_out, y3, st3, bname + '.bn3', p3, mask_mode=2, mask_src=out, want_g=not down)
+            xin16, y1, st1, a1, y2, st2, a2, y3, st3, xd16, yd, std, out, (h, w, ho, wo), (p1, p2, p3), bits = sv       # operand modes of conv1 (+ downsample), conv2, conv3
+            # out = relu(bn3(y3) + skip): g = d_out * [out > 0] reaches bn3 and the skip branch alike.  ``bits``: the pattern [out > 0] as one bit per
+            # element (LP_E_MASKBITS) -- g is then never written: the identity branch takes it from d_out and the bits in conv1's data-gradient epilogue,
+            # and a downsample block's two BatchNorms (same g) share one pass pair where they share the operand mode and the residency of y
+            pattern = out if bits is None else bits
+            dd16 = None
+            if down and bits is not None and p3 == p1 and isinstance(y3, ops.Act16) == isinstance(yd, ops.Act16):
+                gm = lambda k: par[k].detach()
+                (d16, dg, db), (dd16, dgd, dbd) = ops.bn_bwd16_dual(d_out, y3, (gm(bname + '.bn3.weight'), st3.mean, st3.rstd), yd,
+                                                                    (gm(bname + '.downsample.1.weight'), std.mean, std.rstd), prec=p3, mask_src=bits, frozen=frozen)
+                grads[bname + '.bn3.weight'], grads[bname + '.bn3.bias'] = dg, db
+                grads[bname + '.downsample.1.weight'], grads[bname + '.downsample.1.bias'] = dgd, dbd
+            else:
+                d16, g = bn_bwd(d_out, y3, st3, bname + '.bn3', p3, mask_mode=2, mask_src=pattern, want_g=not down and bits is None)
             wgrad(bname + '.conv3.weight', lambda a, d, k=bname + '.conv3.weight', p=p3: _wgrad1x1(a, d, p).view(par[k].shape), a2, d16)
             dA2 = _conv1x1(d16, packs[bname + '.conv3.weight'][1], p3).view(n, ho, wo, width)
             d16, _ = bn_bwd(dA2, y2, st2, bname + '.bn2', p2)
@@ -263,7 +284,8 @@ class ResNeXtFunction(torch.autograd.Function):
             d16, _ = bn_bwd(dA1, y1, st1, bname + '.bn1', p1)
             wgrad(bname + '.conv1.weight', lambda a, d, k=bname + '.conv1.weight', p=p1: _wgrad1x1(a, d, p).view(par[k].shape), xin16, d16)
             if down:
-                dd16, _ = bn_bwd(d_out, yd, std, bname + '.downsample.1', p1, mask_mode=2, mask_src=out)      # same ReLU pattern as bn3: out > 0
+                if dd16 is None:
+                    dd16, _ = bn_bwd(d_out, yd, std, bname + '.downsample.1', p1, mask_mode=2, mask_src=pattern)      # same ReLU pattern as bn3: out > 0
                 wgrad(bname + '.downsample.0.weight', lambda a, d, k=bname + '.downsample.0.weight', p=p1: _wgrad1x1(a, d, p).view(par[k].shape), xd16, dd16)
                 d_xd = _conv1x1(dd16, packs[bname + '.downsample.0.weight'][1], p1)          # [P', cin]
                 if stride == 2:
@@ -271,6 +293,8 @@ class ResNeXtFunction(torch.autograd.Function):
                     ops.add_strided2(d_xin, d_xd.view(n, ho, wo, cin))
                 else:
                     d_xin = _conv1x1(d16, packs[bname + '.conv1.weight'][1], p1, res=d_xd).view(n, h, w, cin)
+            elif bits is not None:
+                d_xin = _conv1x1(d16, packs[bname + '.conv1.weight'][1], p1, res=d_out, res_bits=bits).view(n, h, w, cin)
             else:
                 d_xin = _conv1x1(d16, packs[bname + '.conv1.weight'][1], p1, res=g).view(n, h, w, cin)
             d_out = d_xin

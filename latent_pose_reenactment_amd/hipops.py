@@ -282,8 +282,11 @@ class ConvStats(NamedTuple):
 def conv16(a: Act16, pack: WeightPack, *, ksize: int, upsample: bool = False, bias: Optional[Tensor] = None,
            res: Optional[Tensor] = None, res_shift: int = 0, alpha: Optional[Tensor] = None, prec: int = PREC_BF16,
            relu_mask: Optional[Act16] = None, out16: Optional[int] = None, amax: bool = False, stats: bool = False, want_y: bool = True,
-           kind: str = 'conv_igemm', phase: bool = False, phase_dgrad: bool = False, y_relu: bool = False):
+           kind: str = 'conv_igemm', phase: bool = False, phase_dgrad: bool = False, y_relu: bool = False, res_bits: Optional[Tensor] = None):
     """y = alpha * conv(up2?(a), pack) + bias + res on operand planes; a [N,Hin,Win,C8] -> y [N,H,W,Cout] fp32.
+    ``res_bits`` (uint8 [N,H,W,Cout/8], the one-bit pattern of ``bn_add_act(want_bits=True)``; Cout % 8 == 0, no ``res_shift``): the residual is
+    GATED, y += res where the bit is set and += 0 elsewhere (lp_conv16_fwd_gated) -- the skip gradient d_out * [out > 0] of a residual block taken
+    from d_out itself.
     ``relu_mask``: operand planes [N,H,W,Co8] of the forward conv's input; y is zeroed where they are <= 0 (fused ReLU backward
     when this launch is a data gradient).  ``out16`` = 0 | 1: also return the operand planes of y (1: of relu(y)) -> (y, Act16).
     ``stats``: the epilogue also leaves the norm-statistics partials of y -> (..., ConvStats | None) appended (None: geometry not covered
@@ -313,6 +316,9 @@ def conv16(a: Act16, pack: WeightPack, *, ksize: int, upsample: bool = False, bi
         assert res.shape == (n, h >> res_shift, w >> res_shift, cout), (res.shape, (n, h, w, cout), res_shift)
     if relu_mask is not None:
         assert relu_mask.hi.shape == (n, h, w, _round_up(cout, 8)), (relu_mask.hi.shape, (n, h, w, cout))
+    if res_bits is not None:
+        assert res is not None and res_shift == 0 and cout % 8 == 0 and res_bits.dtype == torch.uint8 and res_bits.is_cuda and \
+            res_bits.is_contiguous() and res_bits.shape == (n, h, w, cout // 8), (res_bits.shape, (n, h, w, cout), res_shift)
     o_hi = o_lo = None
     if out16 is not None:
         o_hi, o_lo = _alloc16(n, h, w, cout, prec, dev)
@@ -326,18 +332,23 @@ def conv16(a: Act16, pack: WeightPack, *, ksize: int, upsample: bool = False, bi
         st_buf = torch.empty(st_cap, dtype=torch.float32, device=dev)
         st_rows = ctypes.c_int(0)
     pl = 4 if prec == PREC_BF16X3 else 2              # bytes per operand-plane element
-    nbytes = (n * hin * win * a.hi.shape[3] * pl + pack.hi.numel() * pl + (n * (h >> res_shift) * (w >> res_shift) * cout * 4 if res is not None else 0),
+    nbytes = (n * hin * win * a.hi.shape[3] * pl + pack.hi.numel() * pl + (n * (h >> res_shift) * (w >> res_shift) * cout * 4 if res is not None else 0)
+              + (res_bits.numel() if res_bits is not None else 0),
               n * h * w * cout * ((4 if want_y else 0) + (pl if out16 is not None else 0)))          # (read: planes once + weights + residual, write)
     # (roofline accounting: the DENSE count of the conv as the reference executes it -- the phase forms do 4/9 of it; the data-gradient form's dense
     #  conv lives on the 2h x 2w grid)
     dh, dw_ = (2 * h, 2 * w) if phase_dgrad else (h, w)
     with _Timed(kind, 2.0 * n * dh * dw_ * cout * cin * ksize * ksize, (n, dh, dw_, cin, cout, ksize, 3 if phase_dgrad else 2 if phase else int(upsample), 0), nbytes,
                 mm=3 if prec == PREC_BF16X3 else 1):
-        check(_lib.lib().lp_conv16_fwd_stats(a.hi.data_ptr(), _p(a.lo), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(res),
-                                             _p(alpha), _p(a.inv), n, h, w, cin, cout, pack.cols_p, pack.rows_p, ksize, 3 if phase_dgrad else 2 if phase else int(upsample),
-                                             res_shift, prec, None if relu_mask is None else relu_mask.hi.data_ptr(), _p(o_hi), _p(o_lo),
-                                             int(bool(out16)) | (2 if y_relu else 0), _p(ws), ws_bytes, _p(slots), _p(st_buf), st_cap,
-                                             None if st_rows is None else ctypes.addressof(st_rows), _stream()), 'lp_conv16_fwd')
+        tail = (_p(alpha), _p(a.inv), n, h, w, cin, cout, pack.cols_p, pack.rows_p, ksize, 3 if phase_dgrad else 2 if phase else int(upsample),
+                res_shift, prec, None if relu_mask is None else relu_mask.hi.data_ptr(), _p(o_hi), _p(o_lo),
+                int(bool(out16)) | (2 if y_relu else 0), _p(ws), ws_bytes, _p(slots), _p(st_buf), st_cap,
+                None if st_rows is None else ctypes.addressof(st_rows), _stream())
+        if res_bits is not None:
+            check(_lib.lib().lp_conv16_fwd_gated(a.hi.data_ptr(), _p(a.lo), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(res), res_bits.data_ptr(), *tail),
+                  'lp_conv16_fwd')
+        else:
+            check(_lib.lib().lp_conv16_fwd_stats(a.hi.data_ptr(), _p(a.lo), pack.hi.data_ptr(), _p(pack.lo), _p(y), _p(bias), _p(res), *tail), 'lp_conv16_fwd')
     out = (y,) if out16 is None else (y, Act16(o_hi, o_lo, cout, None))
     if stats:
         out = out + ((ConvStats(st_buf, st_rows.value, n) if st_rows.value > 0 else None),)
@@ -2354,6 +2365,9 @@ def _flat_pc(dA: Tensor, x, mask_src):
     for t, name in ((x, 'x'), (mask_src, 'mask_src')):
         if isinstance(t, Act16):
             assert t.hi.shape == dA.shape, (name, t.hi.shape, dA.shape)
+        elif t is not None and t.dtype == torch.uint8:          # the one-bit pattern of bn_add_act(want_bits=True)
+            assert name == 'mask_src' and t.is_cuda and t.is_contiguous() and dA.shape[-1] % 8 == 0 and \
+                tuple(t.shape) == tuple(dA.shape[:-1]) + (dA.shape[-1] // 8,), (name, t.shape, dA.shape)
         elif t is not None:
             _chk(t, name); assert t.shape == dA.shape, (name, t.shape, dA.shape)
     c = dA.shape[-1]
@@ -2541,10 +2555,13 @@ def maxpool_bwd(dout: Tensor, idx: Tensor, h: int, w: int) -> Tensor:
 
 
 def bn_add_act(y: Tensor, scale: Tensor, shift: Tensor, res: Optional[Tensor] = None, res_scale: Optional[Tensor] = None,
-               res_shift: Optional[Tensor] = None, relu: bool = True, prec: Optional[int] = None, want_out: bool = True):
+               res_shift: Optional[Tensor] = None, relu: bool = True, prec: Optional[int] = None, want_out: bool = True, want_bits: bool = False):
     """out = relu?(y*scale[c]+shift[c] + (res | res*res_scale[c]+res_shift[c])) over [..., C]; with ``prec`` -> (out, Act16).
     ``res`` as ``Act16`` (bf16 / bf16x3 planes of the same mode as ``prec``): the residual is read from the operand planes (lp_bn_add_act_planes);
-    ``want_out=False`` then skips the fp32 copy -> (None, Act16)."""
+    ``want_out=False`` then skips the fp32 copy -> (None, Act16).  ``want_bits`` (with ``prec``): -> (out, Act16, bits), bits uint8 [..., C / 8] =
+    the pattern "HI plane word > 0" as one bit per element (bit j of byte g: channel 8 g + j) -- what ``bn_bwd16`` (mask_mode 4) and
+    ``conv16(res_bits=)`` read in the backward of a residual block."""
+    assert not want_bits or prec is not None, 'want_bits: the pattern is the one of the operand planes'
     if isinstance(res, Act16):
         _chk(y, 'y')
         assert prec in (PREC_BF16, PREC_BF16X3) and res_scale is None and res.inv is None and (res.lo is not None) == (prec == PREC_BF16X3)
@@ -2553,9 +2570,10 @@ def bn_add_act(y: Tensor, scale: Tensor, shift: Tensor, res: Optional[Tensor] = 
         out = torch.empty_like(y) if want_out else None
         hi = torch.empty(y.shape, dtype=torch.int16, device=y.device)
         lo = torch.empty_like(hi) if prec == PREC_BF16X3 else None
-        check(_lib.lib().lp_bn_add_act_planes(y.data_ptr(), scale.data_ptr(), shift.data_ptr(), res.hi.data_ptr(), _p(res.lo), _p(out), hi.data_ptr(), _p(lo),
-                                              y.numel() // c, c, int(relu), prec, _stream()), 'lp_bn_add_act_planes')
-        return out, Act16(hi, lo, c, None)
+        bits = torch.empty(y.shape[:-1] + (c // 8,), dtype=torch.uint8, device=y.device) if want_bits else None
+        check(_lib.lib().lp_bn_add_act_planes_bits(y.data_ptr(), scale.data_ptr(), shift.data_ptr(), res.hi.data_ptr(), _p(res.lo), _p(out), hi.data_ptr(),
+                                                   _p(lo), _p(bits), y.numel() // c, c, int(relu), prec, _stream()), 'lp_bn_add_act_planes')
+        return (out, Act16(hi, lo, c, None), bits) if want_bits else (out, Act16(hi, lo, c, None))
     y16 = y if isinstance(y, Act16) else None
     if y16 is not None:          # 16-bit-resident conv output (fp16 mode)
         assert prec in (None, PREC_F16) and y16.lo is None and y16.inv is None
@@ -2573,14 +2591,17 @@ def bn_add_act(y: Tensor, scale: Tensor, shift: Tensor, res: Optional[Tensor] = 
     if prec is not None:
         hi = torch.empty(shape, dtype=torch.int16, device=dev)
         lo = torch.empty_like(hi) if prec == PREC_BF16X3 else None
+    bits = torch.empty(tuple(shape[:-1]) + (c // 8,), dtype=torch.uint8, device=dev) if want_bits else None
     if res is not None:
         _chk(res, 'res'); assert res.shape == shape, (res.shape, shape)
     if y16 is not None:
-        check(_lib.lib().lp_bn_add_act16(y16.hi.data_ptr(), scale.data_ptr(), shift.data_ptr(), _p(res), _p(res_scale), _p(res_shift),
-                                         _p(out), _p(hi), p, c, int(relu), _stream()), 'lp_bn_add_act16')
+        check(_lib.lib().lp_bn_add_act16_bits(y16.hi.data_ptr(), scale.data_ptr(), shift.data_ptr(), _p(res), _p(res_scale), _p(res_shift),
+                                              _p(out), _p(hi), _p(bits), p, c, int(relu), _stream()), 'lp_bn_add_act16')
     else:
-        check(_lib.lib().lp_bn_add_act(y.data_ptr(), scale.data_ptr(), shift.data_ptr(), _p(res), _p(res_scale), _p(res_shift), _p(out),
-                                       _p(hi), _p(lo), p, c, int(relu), prec if prec is not None else 0, _stream()), 'lp_bn_add_act')
+        check(_lib.lib().lp_bn_add_act_bits(y.data_ptr(), scale.data_ptr(), shift.data_ptr(), _p(res), _p(res_scale), _p(res_shift), _p(out),
+                                            _p(hi), _p(lo), _p(bits), p, c, int(relu), prec if prec is not None else 0, _stream()), 'lp_bn_add_act')
+    if want_bits:
+        return out, Act16(hi, lo, c, None), bits
     return out if prec is None else (out, Act16(hi, lo, c, None))
 
 
@@ -2699,18 +2720,28 @@ def dwconv3x3_wgrad(x: Tensor, dy: Tensor, stride: int, in_scale: Optional[Tenso
     return dw
 
 
+def _mask16_mode(mask_mode: int, mask_src) -> int:
+    """lp_bn_bwd16_h's mask mode for ``mask_src`` given as mode 2: 3 = its 16-bit planes (2 B per element), 4 = its one-bit pattern"""
+    if isinstance(mask_src, Act16):
+        assert mask_mode == 2, mask_mode
+        return 3
+    if mask_src is not None and mask_src.dtype == torch.uint8:
+        assert mask_mode == 2, mask_mode
+        return 4
+    return mask_mode
+
+
 def bn_bwd16(dA: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, scale: Tensor, shift: Tensor, *, prec: int, mask_mode: int = 0,
              mask_src: Optional[Tensor] = None, want_g: bool = False, act_hi: float = 0.0, frozen: bool = False):
     """backward of act(BatchNorm(x)) over x [..., C] written straight to the OPERAND PLANES of dy (what the weight / data gradient
     contractions consume): -> (Act16 of dy, dgamma [C], dbeta [C], g | None).  No fp32 dy, no masked-gradient temporary; in fp16 mode the
     planes carry the power-of-two scale of lp_bn_bwd16 (``Act16.inv``).  Arguments as ``norm_act_bwd``; ``x`` may be a 16-bit-resident
-    conv output (``Act16``, fp16 mode) and ``mask_src`` (mask_mode 2) the operand planes of the activated tensor instead of its fp32 copy."""
+    conv output (``Act16``, fp16 mode) and ``mask_src`` (mask_mode 2) the operand planes of the activated tensor instead of its fp32 copy, or
+    (uint8 [..., C / 8]) its one-bit pattern from ``bn_add_act(want_bits=True)``."""
     shape, p, c, mptr = _flat_pc(dA, x, mask_src)
     x16 = x if isinstance(x, Act16) else None          # 16-bit-resident conv output (fp16 mode)
     assert c % 8 == 0 and (x16 is None or (prec == PREC_F16 and x16.lo is None and x16.inv is None)), (c, prec)
-    if isinstance(mask_src, Act16):                    # the ReLU pattern from the planes of the activated tensor (2 B per element)
-        assert mask_mode == 2, mask_mode
-        mask_mode = 3
+    mask_mode = _mask16_mode(mask_mode, mask_src)
     dev = dA.device
     hi = torch.empty(shape, dtype=torch.int16, device=dev)
     lo = torch.empty_like(hi) if prec == PREC_BF16X3 else None
@@ -2723,3 +2754,31 @@ def bn_bwd16(dA: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, s
                                    sc.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), p, c, mask_mode, float(act_hi), int(frozen), prec,
                                    _p(g), _stream()), 'lp_bn_bwd16')
     return Act16(hi, lo, c, sc[1:] if prec == PREC_F16 else None), dg, db, g
+
+
+
+def bn_bwd16_dual(dA: Tensor, xa, bn_a, xb, bn_b, *, prec: int, mask_src, frozen: bool = False):
+    """``bn_bwd16`` of TWO BatchNorms that receive the same gradient and the same ReLU pattern -- out = relu(BN_a(xa) + BN_b(xb)): bn3 and the
+    downsample BatchNorm of a residual block -- in one pass pair (lp_bn_bwd16_dual): dA and the pattern are read once per pass.  ``bn_a`` / ``bn_b``:
+    (gamma, mean, rstd); ``mask_src`` as ``bn_bwd16``'s with mask_mode 2 (fp32, ``Act16`` or the uint8 bit pattern).  -> ((Act16, dgamma, dbeta) of a,
+    the same of b), bit-identical to two ``bn_bwd16`` calls.  xa and xb must both be fp32 or both 16-bit resident."""
+    shape, p, c, mptr = _flat_pc(dA, xa, mask_src)
+    _flat_pc(dA, xb, None)
+    x16 = isinstance(xa, Act16)
+    assert x16 == isinstance(xb, Act16), 'bn_bwd16_dual: both x as fp32 or both 16-bit resident'
+    assert c % 8 == 0 and (not x16 or (prec == PREC_F16 and xa.lo is None and xa.inv is None and xb.lo is None and xb.inv is None)), (c, prec)
+    mask_mode = _mask16_mode(2, mask_src)
+    dev = dA.device
+    ws_floats = _lib.lib().lp_bn_bwd16_workspace_bytes(p, c) // 4
+    res, args = [], []
+    for x, (gamma, mean, rstd) in ((xa, bn_a), (xb, bn_b)):
+        hi = torch.empty(shape, dtype=torch.int16, device=dev)
+        lo = torch.empty_like(hi) if prec == PREC_BF16X3 else None
+        small = torch.empty(2 + 2 * c, dtype=torch.float32, device=dev)
+        sc, dg, db = small[:2], small[2:2 + c], small[2 + c:]
+        ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+        args += [None if x16 else x.data_ptr(), x.hi.data_ptr() if x16 else None, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), hi.data_ptr(), _p(lo),
+                 sc.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr()]
+        res.append((Act16(hi, lo, c, sc[1:] if prec == PREC_F16 else None), dg, db, ws))
+    check(_lib.lib().lp_bn_bwd16_dual(dA.data_ptr(), mptr, *args, p, c, mask_mode, int(frozen), prec, _stream()), 'lp_bn_bwd16_dual')
+    return res[0][:3], res[1][:3]
