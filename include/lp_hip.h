@@ -548,6 +548,16 @@ int lp_image_prep_bwd(const float* g, const float* stdv, float* dx, int N, int H
  * LP_ERR_ARG: null pointer, N < 1, P or L outside 1 .. 256, parts outside 1 .. 16, S < 1, width <= 0 -- checked before any device work. */
 int lp_stickman_render(const float* points, int N, int P, const int* seg, const int* part_end, const float* colour, int L, int parts, int S,
                        float width, float* out, void* stream);
+/* (additive, ABI 12) Hard-edged stickman of the keypoint loaders (csrc/stickman_hard.hip holds the definition; the reference's
+ * SampleLoader.draw_stickman: cv2.polylines of thickness T on rounded integer keypoints, restated exactly in integers): points [N][P][2] (x, y) in
+ * [0, 1] -> out [N][3][S][S] fp32 NCHW, contiguous.  A coordinate becomes clamp(rint(x * S), -4096, 8191) (fp32 product, half to even, NaN -> -4096);
+ * a pixel is covered by a segment iff its distance to it is <= T / 2 (round caps; integer tests) and takes the colour of the LAST part in table order
+ * that covers it, 0 where none does.  seg / part_end / colour: the polyline table of lp_stickman_render (DEVICE arrays; indices outside 0 .. P-1 are
+ * clamped, not reported).  One launch, no atomics (bit-reproducible), no allocation, no synchronisation: capturable.
+ * LP_ERR_ARG: null pointer, N < 1, P or L outside 1 .. 256, parts outside 1 .. 16, S outside 1 .. 4096, T outside 1 .. 8; LP_ERR_UNSUPPORTED: more
+ * workgroups than one launch grid holds -- checked before any device work. */
+int lp_stickman_render_hard(const float* points, int N, int P, const int* seg, const int* part_end, const float* colour, int L, int parts, int S,
+                            int T, float* out, void* stream);
 /* (additive, ABI 12) Image-quality table of a batch (csrc/image_quality.hip holds the definition): x, y logical [B][C][H][W] fp32 read in place,
  * stride_x / stride_y = 4 element strides (image, channel, row, column; HOST arrays read at call time); mask (|NULL) logical [B][H][W] fp32 with
  * stride_m = 3 element strides (image, row, column; 0 allowed: an expanded view).  Both images are clamped to [0, 1]; the mask is used as given.

@@ -114,6 +114,7 @@ SIGNATURES = {
     'lp_image_prep_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'lp_image_prep_bwd': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'lp_stickman_render': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    'lp_stickman_render_hard': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'lp_image_quality_workspace_bytes': (_ll, [_i, _i, _i]),
     'lp_image_quality': (_i, [_vp] * 6 + [_i] * 4 + [_vp, _vp, _vp]),
     'lp_augment_triplet': (_i, [_vp] * 7 + [_i] * 5 + [_vp] * 4),

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(HERE, 'liblp_hip.so')
-SOURCES = ['lp_api.hip', 'elementwise.hip', 'norm_bwd.hip', 'tanh_head.hip', 'spectral_norm.hip', 'act_pack.hip', 'conv_dma.hip', 'conv_pipe.hip', 'gconv_rows.hip', 'conv_wgrad.hip', 'conv_thin.hip', 'conv_stem8.hip', 'linear_crop.hip', 'mobilenet.hip', 'resnext.hip', 'reflect_border.hip', 'stickman.hip', 'image_quality.hip', 'augment.hip', 'augment_extra.hip', 'frames.hip', 'frames_pad.hip', 'visual_sheet.hip', 'jpeg.hip', 'jpeg_decode.hip', 'png.hip']
+SOURCES = ['lp_api.hip', 'elementwise.hip', 'norm_bwd.hip', 'tanh_head.hip', 'spectral_norm.hip', 'act_pack.hip', 'conv_dma.hip', 'conv_pipe.hip', 'gconv_rows.hip', 'conv_wgrad.hip', 'conv_thin.hip', 'conv_stem8.hip', 'linear_crop.hip', 'mobilenet.hip', 'resnext.hip', 'reflect_border.hip', 'stickman.hip', 'stickman_hard.hip', 'image_quality.hip', 'augment.hip', 'augment_extra.hip', 'frames.hip', 'frames_pad.hip', 'visual_sheet.hip', 'jpeg.hip', 'jpeg_decode.hip', 'png.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I', INCLUDE, '-I', CSRC]
 
 

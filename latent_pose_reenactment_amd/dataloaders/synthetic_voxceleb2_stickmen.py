@@ -19,6 +19,17 @@ PARTS = ((0, 16, False, (0.0, 1.0, 0.0)),      # jaw
          (48, 59, True, (1.0, 0.0, 1.0)),      # lips
          (60, 67, True, (1.0, 0.0, 1.0)))
 
+# the reference's own topology and colours (dataloaders/common/voxceleb.py:128-152), in its drawing order -- later parts overwrite earlier ones;
+# points 60-67 (the inner mouth) are not drawn.  What the keypoint loaders (dataloaders/voxceleb2.py) draw with hipops.stickman_render_hard.
+REFERENCE_PARTS_NO_OVAL = ((17, 21, False, (1.0, 0.0, 0.0)),      # brows
+                           (22, 26, False, (0.0, 1.0, 0.0)),
+                           (27, 30, False, (0.0, 0.0, 1.0)),      # nose bridge, nose base
+                           (31, 35, False, (0.0, 0.0, 1.0)),
+                           (36, 41, True, (1.0, 0.0, 1.0)),       # eyes
+                           (42, 47, True, (0.0, 1.0, 1.0)),
+                           (48, 59, True, (1.0, 1.0, 0.0)))       # outer mouth
+REFERENCE_PARTS = ((0, 16, False, (1.0, 1.0, 1.0)),) + REFERENCE_PARTS_NO_OVAL          # --draw_oval: the jaw, white, drawn first
+
 
 def face_keypoints(g):
     """68 points in [0, 1]^2 on a jittered template face (seeded by ``g``) -> [68, 2] (x, y)"""

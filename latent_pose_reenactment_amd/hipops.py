@@ -9,6 +9,7 @@ import torch
 from . import _lib
 from ._lib import PREC_BF16, PREC_BF16X3, PREC_F16, check
 from .dataloaders.synthetic_voxceleb2_stickmen import PARTS      # the one place that knows the face topology (stickman_render's default table)
+from .dataloaders.synthetic_voxceleb2_stickmen import REFERENCE_PARTS, REFERENCE_PARTS_NO_OVAL      # (stickman_render_hard's)
 
 Tensor = torch.Tensor
 
@@ -1214,7 +1215,102 @@ def stickman_render(points: Tensor, size: int, width: Optional[float] = None, ou
     return out
 
 
-IMAGE_QUALITY_COLUMNS = ('ssim', 'psnr', 'l1', 'ssim_fg', 'psnr_fg', 'l1_fg')
+HARD_POINT_MIN, HARD_POINT_MAX = -4096, 8191          # the clamp of the hard stickman's integer points (csrc/stickman_hard.hip)
+HARD_MAX_SIZE, HARD_MAX_THICKNESS = 4096, 8
+
+
+def _hard_arguments(name, points, size, thickness, parts):
+    """the checks ``stickman_render_hard`` and its host twin share -> (size, thickness, polyline table as host lists, leading shape, P)"""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
+        raise ValueError(f'{name}: fp32 keypoints are required, got {points.dtype if isinstance(points, torch.Tensor) else type(points).__name__}')
+    size, thickness = int(size), int(thickness)
+    if not 1 <= size <= HARD_MAX_SIZE:
+        raise ValueError(f'{name}: size must be in 1 .. {HARD_MAX_SIZE}, got {size}')
+    if not 1 <= thickness <= HARD_MAX_THICKNESS:
+        raise ValueError(f'{name}: thickness must be in 1 .. {HARD_MAX_THICKNESS}, got {thickness}')
+    table = stickman_table(parts)
+    npoints = table[3]
+    if points.dim() >= 2 and points.shape[-1] == 2 and points.shape[-2] >= npoints:
+        lead, p = tuple(points.shape[:-2]), points.shape[-2]
+    elif points.dim() >= 1 and points.shape[-1] % 2 == 0 and points.shape[-1] // 2 >= npoints:
+        lead, p = tuple(points.shape[:-1]), points.shape[-1] // 2
+    else:
+        raise ValueError(f'{name}: keypoints {tuple(points.shape)}: expected [..., P, 2] or [..., 2P] with P >= {npoints}, the points the polyline '
+                         'table names')
+    if p > 256:
+        raise ValueError(f'{name}: at most 256 keypoints per image are supported, got {p}')
+    n = 1
+    for d in lead:
+        n *= d
+    if n < 1:
+        raise ValueError(f'{name}: keypoints {tuple(points.shape)} hold no image')
+    return size, thickness, table, lead, p, n
+
+
+def _hard_out(name, out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f'{name}: out must be a tensor, got {type(out).__name__}')
+    if not (out.device == device and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f'{name}: out must be a contiguous fp32 tensor of shape {shape} on {device}, got '
+                         f'{tuple(out.shape)} {out.dtype} {out.device} contiguous={out.is_contiguous()}')
+    return out
+
+
+def stickman_render_hard(points: Tensor, size: int, thickness: int = 2, out: Optional[Tensor] = None, parts=REFERENCE_PARTS) -> Tensor:
+    """keypoints [..., P, 2] or [..., 2P] ((x, y) pairs in [0, 1]; fp32, on the GPU) -> stickmen [..., 3, S, S], fp32: the reference's
+    ``draw_stickman`` (cv2.polylines of ``thickness`` on rounded integer keypoints, later parts over earlier ones) by the exact-integer definition in
+    the header of csrc/stickman_hard.hip, as ONE launch on the current stream (lp_stickman_render_hard).  ``parts`` defaults to the reference's
+    topology with the face oval (``REFERENCE_PARTS``; ``REFERENCE_PARTS_NO_OVAL`` without).  ``out``: a contiguous fp32 tensor of the result's shape
+    to write into -- it may be a view of a larger tensor.  Points are clamped by the definition, never checked (no host sync); CPU tensors:
+    ``stickman_render_hard_host``."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise ValueError('stickman_render_hard: the keypoints must be a CUDA tensor (the stickman is rendered on the MI355X; for CPU tensors call '
+                         'stickman_render_hard_host)')
+    size, thickness, _, lead, p, n = _hard_arguments('stickman_render_hard', points, size, thickness, parts)
+    seg, part_end, colour, nseg, nparts, _ = _stickman_device_table(parts, points.device)
+    out = _hard_out('stickman_render_hard', out, lead + (3, size, size), points.device)
+    pts = points.detach().contiguous()
+    check(_lib.lib().lp_stickman_render_hard(pts.data_ptr(), n, p, seg.data_ptr(), part_end.data_ptr(), colour.data_ptr(), nseg, nparts, size,
+                                             thickness, out.data_ptr(), _stream()), 'lp_stickman_render_hard')
+    return out
+
+
+def stickman_render_hard_host(points: Tensor, size: int, thickness: int = 2, out: Optional[Tensor] = None, parts=REFERENCE_PARTS) -> Tensor:
+    """``stickman_render_hard`` for CPU tensors: the same definition in numpy integer operations (int64 throughout), bit-identical to the kernel"""
+    import numpy as np
+    if not isinstance(points, torch.Tensor) or points.is_cuda:
+        raise ValueError('stickman_render_hard_host: the keypoints must be a CPU tensor (on the GPU call stickman_render_hard)')
+    size, thickness, (seg, part_end, colour, _), lead, p, n = _hard_arguments('stickman_render_hard_host', points, size, thickness, parts)
+    out = _hard_out('stickman_render_hard_host', out, lead + (3, size, size), points.device)
+    x = points.detach().contiguous().reshape(n, p, 2).numpy()
+    with np.errstate(invalid='ignore', over='ignore'):
+        r = (x * np.float32(size)).round()          # the fp32 product, rounded half to even
+        r = np.where(r >= np.float32(HARD_POINT_MIN), np.minimum(r, np.float32(HARD_POINT_MAX)), np.float32(HARD_POINT_MIN))          # NaN -> lower bound
+    pts = r.astype(np.int64)
+    v, u = np.meshgrid(np.arange(size, dtype=np.int64), np.arange(size, dtype=np.int64), indexing='ij')          # v: row, u: column
+    t2 = thickness * thickness
+    hit = np.full((n, size, size), -1, dtype=np.int64)
+    start = 0
+    for part, end in enumerate(part_end):
+        for i, j in seg[start:end]:
+            a, b = pts[:, i, :, None, None], pts[:, j, :, None, None]          # [n, 2, 1, 1]
+            dx, dy = b[:, 0] - a[:, 0], b[:, 1] - a[:, 1]
+            ex, ey = u[None] - a[:, 0], v[None] - a[:, 1]
+            fx, fy = u[None] - b[:, 0], v[None] - b[:, 1]
+            l2, s = dx * dx + dy * dy, ex * dx + ey * dy
+            cross = dx * ey - dy * ex
+            covered = np.where(s <= 0, 4 * (ex * ex + ey * ey) <= t2, np.where(s >= l2, 4 * (fx * fx + fy * fy) <= t2, 4 * cross * cross <= t2 * l2))
+            hit[covered] = part
+        start = end
+    table = np.concatenate([np.asarray(colour, dtype=np.float32).reshape(-1, 3), np.zeros((1, 3), dtype=np.float32)])          # (-1: no part -> 0)
+    img = np.ascontiguousarray(table[hit].transpose(0, 3, 1, 2))
+    out.copy_(torch.from_numpy(img).reshape(out.shape))
+    return out
+
+
+IMAGE_QUALITY_COLUMNS =('ssim', 'psnr', 'l1', 'ssim_fg', 'psnr_fg', 'l1_fg')
 
 
 def image_quality(x: Tensor, y: Tensor, mask: Optional[Tensor] = None) -> Tensor:
