@@ -11,7 +11,8 @@ One operand is "wide", the other "narrow":
   bf16x3       wide: |v| <= 511 or 1023 -- hi = bf16(v), lo = bf16(v - hi) reproduces every |v| <= 65535; 25 - 50 % of the lo words are non-zero
   narrow       {-2 .. 2}, shrunk to {-1, 0, 1} and then thinned with zeros until the budget holds
 The bf16x3 kernels form hi*hi + hi*lo + lo*hi and drop lo*lo by design: that is the reference (from the decoded planes), and the budget is taken
-on |hi| + |lo|.  CPU-only module: torch on the host, nothing from the library."""
+on |hi| + |lo|.  The phase forms (lp_pack_weights modes 2 .. 5) contract 16 PRE-SUMMED taps: phase_conv64 / phase_bound / draw_phase_pair below.
+CPU-only module: torch on the host, nothing from the library."""
 import torch
 import torch.nn.functional as F
 
@@ -140,6 +141,82 @@ def draw_pair(seed, a_shape, w_shape, prec, wide, bound_fn, big=False, both_wide
         w = draw_ints(g, w_shape, wb if wide == 'w' else nb, 1.0 if wide == 'w' else keep).float() * QW
         try:
             bound_fn(terms(a, prec), terms(w, prec))
+            return a, w
+        except BudgetError as e:
+            last = e
+    raise last
+
+
+# ---- the phase forms (lp_pack_weights modes 2 .. 5, lp_conv16_fwd upsample = 2 | 3; include/lp_hip.h) ---------------------------------------
+# Sixteen pre-summed taps W'[t], t = p * 8 + q * 4 + i * 2 + j, each a [rows][cols] matrix (rows = the launch's output channels, cols = its
+# contraction).  Written from the definitions of the header, on plain strided slices:
+#   scatter (modes 2 and 5, upsample = 2): in [N][cols][h][w] -> out [N][rows][2h][2w],
+#       out[2y + p, 2x + q] = sum_{i, j} W'[t] . in[y + p - 1 + i, x + q - 1 + j]
+#   gather  (modes 3 and 4, upsample = 3): in [N][cols][2h][2w] -> out [N][rows][h][w],
+#       out[y, x] = sum_{p, q, i, j} W'[t] . in[2y + 2i - p, 2x + 2j - q]
+#     mode 4 by its definition (pooled[y] = sum_u W4[u] in[2y + u], W'[t] = W4[2i - p][2j - q]); mode 3 as the adjoint of the scatter form: the pixel
+#     (2y' + p, 2x' + q) that scatter tap (p, q, i', j') fills from (y, x) has y' = y - p + 1 - i', so with i = 1 - i' it is row 2y + 2i - p, and the
+#     mode-3 image holds exactly the (p, q, 1 - i, 1 - j) sums, transposed.
+# Positions outside the input read zero.
+WIDE_W_PHASE = 63                     # single-plane modes: up to 4 taps coincide, |sum| <= 252 stays exact in 8 significand bits
+
+
+def phase_conv(a, w16, gather):
+    """one term of the contraction above, in the dtype of its operands (fp64 or int64: shifted adds and channel contractions only)"""
+    n, c, h, w = a.shape
+    assert w16.shape[0] == 16 and w16.shape[2] == c, (w16.shape, a.shape)
+    rows = w16.shape[1]
+    ap = torch.zeros((n, c, h + 2, w + 2), dtype=a.dtype)
+    ap[:, :, 1:1 + h, 1:1 + w] = a
+    if gather:
+        assert h % 2 == 0 and w % 2 == 0
+        ho, wo = h // 2, w // 2
+        out = torch.zeros((n, rows, ho, wo), dtype=a.dtype)
+    else:
+        out = torch.zeros((n, rows, 2 * h, 2 * w), dtype=a.dtype)
+    for t in range(16):
+        p, q, i, j = (t >> 3) & 1, (t >> 2) & 1, (t >> 1) & 1, t & 1
+        if gather:       # input row 2y + 2i - p sits at padded index 2y + 2i - p + 1
+            src = ap[:, :, 2 * i - p + 1:2 * i - p + 1 + 2 * ho:2, 2 * j - q + 1:2 * j - q + 1 + 2 * wo:2]
+            out += torch.einsum('nchw,oc->nohw', src, w16[t])
+        else:            # input row y + p - 1 + i sits at padded index y + p + i
+            src = ap[:, :, p + i:p + i + h, q + j:q + j + w]
+            out[:, :, p::2, q::2] += torch.einsum('nchw,oc->nohw', src, w16[t])
+    return out
+
+
+def phase_conv64(a_terms, w16_terms, gather):
+    """fp64 contraction of a phase-form launch from the 16 PRE-SUMMED taps: hi*hi (+ hi*lo + lo*hi over the split of the pre-summed value -- the
+    split happens after the sum, so the split of the dense 3x3 weight is not the reference)"""
+    ref = phase_conv(a_terms[0], sum(w16_terms), gather)
+    if len(a_terms) == 2:
+        ref = ref + phase_conv(a_terms[1], w16_terms[0], gather)
+    return ref
+
+
+def phase_bound(a_terms, w16_terms, gather, alpha, bias=None, res=None):
+    """alpha * phase_conv(|A|, |W'|) + |bias| + |res| in fp64 (bias [rows], res NCHW at output resolution, or None): no partial sum of the launch,
+    of one split-K slice or of one phase, exceeds it"""
+    b = alpha * phase_conv(abs_sum(a_terms), abs_sum(w16_terms), gather)
+    if bias is not None:
+        b = b + bias.double().abs()[None, :, None, None]
+    if res is not None:
+        b = b + res.double().abs()
+    return b
+
+
+def draw_phase_pair(seed, a_shape, w_shape, prec, wide, bound_fn, big=False):
+    """draw_pair for the phase forms: w [.][.][3][3] are integers times QW whose tap sums must stay exact -- a wide weight of the single-plane modes
+    is bounded by WIDE_W_PHASE, bf16x3 keeps 511 / 1023 (hi + lo reproduces every sum).  bound_fn(a, w) takes the fp32 tensors."""
+    wb = wide_bound(prec, big)
+    wwb = wb if prec == PREC_BF16X3 else WIDE_W_PHASE
+    last = None
+    for nb, keep in NARROW_STEPS:
+        g = torch.Generator().manual_seed(seed)
+        a = draw_ints(g, a_shape, wb if wide == 'a' else nb, 1.0 if wide == 'a' else keep).float() * QA
+        w = draw_ints(g, w_shape, wwb if wide == 'w' else nb, 1.0 if wide == 'w' else keep).float() * QW
+        try:
+            bound_fn(a, w)
             return a, w
         except BudgetError as e:
             last = e

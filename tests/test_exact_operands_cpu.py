@@ -1,6 +1,7 @@
-"""CPU proof of tests/exact_operands.py, before tests/test_conv_dma_exact.py and tests/test_wgrad_exact.py hold kernels to it bit for bit: the hi / lo
-split identity, the budget assertion, the fp64 references against integer arithmetic, and the decoded planes of the bit-level packers of
-tests/operand_restatement.py against the inputs.  No GPU, nothing from the library."""
+"""CPU proof of tests/exact_operands.py, before tests/test_conv_dma_exact.py, tests/test_conv_phase_exact.py, tests/test_conv_pipe_exact.py and
+tests/test_wgrad_exact.py hold kernels to it bit for bit: the hi / lo split identity, the budget assertion, the fp64 references against integer
+arithmetic, the phase forms of the 16 pre-summed taps against the dense operations and against their adjoints in int64, and the decoded planes of the
+bit-level packers of tests/operand_restatement.py against the inputs.  No GPU, nothing from the library."""
 import os
 import sys
 
@@ -106,6 +107,94 @@ def test_fp64_references_equal_integer_arithmetic(prec, ks, ups):
                 ap[:, :, pad:pad + h, pad:pad + w] = src
                 want[:, :, ky, kx] += torch.einsum('nchw,nohw->oc', ap[:, :, ky:ky + h, kx:kx + w], d)
     assert torch.equal(dw, want.double() * (E.QA * E.QW / (s * s)))
+
+
+def _int_taps(wi, mode):
+    """the 16 pre-summed taps of R.weight_values as int64 [16][rows][cols]; modes 4 / 5 carry the factor 1/4 and are returned TIMES FOUR"""
+    v = R.weight_values(wi.numpy().astype(np.float64), mode) * (4.0 if mode >= 4 else 1.0)
+    assert np.array_equal(v, np.round(v))
+    return torch.from_numpy(v.astype(np.int64))
+
+
+def _box2(t):
+    return t[:, :, 0::2, 0::2] + t[:, :, 0::2, 1::2] + t[:, :, 1::2, 0::2] + t[:, :, 1::2, 1::2]
+
+
+PHASE_GEOMETRIES = [(2, 5, 7, 3, 4), (1, 3, 2, 6, 5), (3, 2, 2, 1, 1), (1, 1, 1, 2, 3)]      # N, Cin, Cout, low-resolution h, w
+
+
+@pytest.mark.parametrize('geo', PHASE_GEOMETRIES)
+def test_scatter_form_of_the_mode_2_taps_is_the_upsampled_conv(geo):
+    """int64: the 16-tap scatter form == conv3x3(nearest_up2(x)) with the original 3x3 weights"""
+    n, cin, cout, h, w = geo
+    g = torch.Generator().manual_seed(sum(geo))
+    x, wi = E.draw_ints(g, (n, cin, h, w), 255), E.draw_ints(g, (cout, cin, 3, 3), 63)
+    got = E.phase_conv(x, _int_taps(wi, 2), gather=False)
+    assert got.dtype == torch.int64 and torch.equal(got, E.conv_int64(x, wi, ups=True))
+
+
+@pytest.mark.parametrize('geo', PHASE_GEOMETRIES)
+def test_gather_form_of_the_mode_4_taps_is_the_box_sum_of_the_dense_conv(geo):
+    """int64: the gather form with 4 x the mode-4 taps == the 2 x 2 box sum of conv3x3(x), i.e. 4 x AvgPool2d(2)"""
+    n, cin, cout, h, w = geo
+    g = torch.Generator().manual_seed(sum(geo) + 1)
+    x, wi = E.draw_ints(g, (n, cin, 2 * h, 2 * w), 255), E.draw_ints(g, (cout, cin, 3, 3), 63)
+    got = E.phase_conv(x, _int_taps(wi, 4), gather=True)
+    assert torch.equal(got, _box2(E.conv_int64(x, wi)))
+
+
+@pytest.mark.parametrize('fwd,bwd', [(2, 3), (4, 5)])
+@pytest.mark.parametrize('geo', PHASE_GEOMETRIES)
+def test_data_gradient_modes_are_the_adjoints_of_the_forward_modes(geo, fwd, bwd):
+    """int64: <f(x), d> == <x, f^T(d)> -- mode 3 (gather) is the adjoint of mode 2 (scatter), mode 5 (scatter) of mode 4 (gather)"""
+    n, cin, cout, h, w = geo
+    g = torch.Generator().manual_seed(sum(geo) + fwd)
+    wi = E.draw_ints(g, (cout, cin, 3, 3), 63)
+    x = E.draw_ints(g, (n, cin, h, w) if fwd == 2 else (n, cin, 2 * h, 2 * w), 255)
+    d = E.draw_ints(g, (n, cout, 2 * h, 2 * w) if fwd == 2 else (n, cout, h, w), 255)
+    fx = E.phase_conv(x, _int_taps(wi, fwd), gather=(fwd == 4))
+    ftd = E.phase_conv(d, _int_taps(wi, bwd), gather=(bwd == 3))
+    assert fx.shape == d.shape and ftd.shape == x.shape
+    assert int((fx * d).sum()) == int((x * ftd).sum())
+    # ... and element by element against the adjoint written out: the gradient of <f(x), d> w.r.t. every x is the response to a unit impulse
+    lin = torch.zeros_like(x)
+    for idx in ((0, 0, 0, 0), (n - 1, cin - 1, x.shape[2] - 1, x.shape[3] - 1), (0, cin - 1, x.shape[2] // 2, 0)):
+        e = torch.zeros_like(x)
+        e[idx] = 1
+        lin[idx] = int((E.phase_conv(e, _int_taps(wi, fwd), gather=(fwd == 4)) * d).sum())
+        assert lin[idx] == ftd[idx], (idx, lin[idx], ftd[idx])
+
+
+@pytest.mark.parametrize('prec', [E.PREC_BF16, E.PREC_BF16X3, E.PREC_F16])
+def test_phase_conv64_on_the_terms_of_the_pre_summed_taps(prec):
+    """the fp64 phase references against integer arithmetic on the terms (hi * (hi + lo) + lo * hi over the split of the PRE-SUMMED value); in the
+    single-plane modes they equal the dense definitions -- conv64(ups) and the average pool of conv64 -- because the tap sums are exact"""
+    g = torch.Generator().manual_seed(40 + prec)
+    n, cin, cout, h, w = 2, 12, 6, 4, 6
+    b = E.wide_bound(prec, big=True)
+    s = 256
+    for mode in (2, 3, 4, 5):
+        gather = mode in (3, 4)
+        qw = E.QW / 4 if mode >= 4 else E.QW
+        wi = E.draw_ints(g, (cout, cin, 3, 3), b if prec == E.PREC_BF16X3 else E.WIDE_W_PHASE)
+        wt = wi.float() * E.QW
+        taps = torch.from_numpy(R.weight_values(wt.numpy(), mode))
+        cols = taps.shape[2]
+        ai = E.draw_ints(g, (n, cols, 2 * h, 2 * w) if gather else (n, cols, h, w), 2)
+        at, tt = E.terms(ai.float() * E.QA, prec), E.terms(taps, prec)
+        ref = E.phase_conv64(at, tt, gather)
+        ti = [[(t / q * s).round().long() for t in ts] for ts, q in ((at, E.QA), (tt, qw))]
+        assert all(torch.equal(i.double() / s * q, t) for ts, it, q in ((at, ti[0], E.QA), (tt, ti[1], qw)) for t, i in zip(ts, it))
+        want = E.phase_conv(ti[0][0], sum(ti[1]), gather)
+        if prec == E.PREC_BF16X3:
+            want = want + E.phase_conv(ti[0][1], ti[1][0], gather)
+        assert torch.equal(ref, want.double() * (E.QA * qw / (s * s))), mode
+        bound = E.phase_bound(at, tt, gather, 1.0)
+        assert bool((ref.abs() <= bound).all())
+        if prec != E.PREC_BF16X3 and mode == 2:
+            assert torch.equal(ref, E.conv64(at, E.terms(wt, prec), ups=True))
+        if prec != E.PREC_BF16X3 and mode == 4:
+            assert torch.equal(ref, torch.nn.functional.avg_pool2d(E.conv64(at, E.terms(wt, prec)), 2))
 
 
 @pytest.mark.parametrize('prec', [E.PREC_BF16, E.PREC_BF16X3, E.PREC_F16])
